@@ -8,8 +8,16 @@ HBM-roofline fraction of the job (B_alg = 20 B x records + 12 B x
 crdt_merge of the whole batch (R = 1024 sequential Crdt.merge calls, crdt.dart:77-94)
 with every input already resident in HBM.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run does what the headline figure needs: it generates the workload, lets the library's
+tuners settle, warms up, times the K steps and prints the result line.  --full adds everything
+else the line can carry (the distinct-key census and the roofline fraction, the win-flag steps,
+the CPU baselines and the full-table parity against the oracle, the host-buffer sample, the GPU
+clock samples, and at N > 1 the routing A/B and the pre-sharded figure); the --no-* switches and
+--flag-steps choose among those legs.  --dump-outputs DIR writes what the last timed step left
+(the merge result and a fixed sample of table rows) as DIR/<name>.npy.
 
 N = 1: one ctx merges the whole batch.
 N > 1 (strong scaling, config 4): the SAME 1B records; replica j arrives whole on rank
@@ -178,6 +186,12 @@ def parse():
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=5)
     p.add_argument("--warmup", type=int, default=2)
+    p.add_argument("--full", action="store_true",
+                   help="also run every leg beside the headline figure: census / roofline fraction, win-flag steps, "
+                        "CPU baselines and parity, host-buffer sample, GPU clocks, N > 1 routing A/B and pre-sharded")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="write what the last timed step computed (merge result, a fixed seeded sample of table rows) "
+                        "as DIR/<name>.npy (float64)")
     p.add_argument("--config", choices=["fanin", "cfg2", "cfg3", "cfg5"], default="fanin")
     p.add_argument("--records", type=int, default=1_000_000_000)
     p.add_argument("--replicas", type=int, default=1024)
@@ -215,7 +229,18 @@ def parse():
     p.add_argument("--ab", default=None, metavar="VAR=v1,v2",
                    help="development A/B: the timed steps alternate the library switch VAR over the values "
                         "(one process, one memory placement); per-value step times go to stderr")
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    if not args.full:                  # a plain run: the headline figure only
+        idle = [o for o in ("--flag-steps", "--cpu-seconds", "--cpu-changesets", "--no-cpu", "--no-cpu-copy16",
+                            "--no-census", "--no-pcie", "--no-presharded")
+                if any(a == o or a.startswith(o + "=") for a in sys.argv[1:])]
+        if idle:
+            log(f"{', '.join(idle)}: only with --full (a plain run skips the legs these switches choose among)")
+        args.no_census = args.no_cpu = args.no_pcie = args.no_presharded = True
+        args.flag_steps = 0
+    return args
 
 
 def main():
@@ -450,9 +475,11 @@ def main():
         step()
         if world > 1:
             log(f"warmup {i}: {(time.perf_counter() - ts) * 1e3:.1f} ms")
-    sampler = GpuSampler(local_rank).start()
+    sampler = GpuSampler(local_rank).start() if args.full else None
     step_ms, tsum, res = timed_run(args.steps, sampler)
-    gpu_clocks = sampler.stop()
+    if args.dump_outputs:                           # (before any later merge touches the table)
+        dump_outputs(args.dump_outputs, table, wl["capacity"], res, rank)
+    gpu_clocks = sampler.stop() if sampler else None
     if gpu_clocks is not None and world == 1:       # this process's streaming copy rate (a 4 GiB device copy)
         a = torch.empty(1 << 30, dtype=torch.int32, device=dev)
         b = torch.empty_like(a)
@@ -660,7 +687,7 @@ def main():
     # packed maxima), route = plain record routing (owners run the whole sorted path), route_l1_head = route_l1
     # with every owner's first level-1 digit folded at the sender; DESIGN §7
     route_ab = None
-    if world > 1 and args.config == "fanin":
+    if world > 1 and args.config == "fanin" and args.full:
         route_ab = {"default_plan": {k: v for k, v in plan.items()
                                      if k in ("route_l1", "combined", "wire_packed", "rl1_pieces", "rl1_head")}}
         modes = {"route_l1": {"CRDT_COMBINE": "0", "CRDT_ROUTE_L1": "1", "CRDT_RL1_SPLIT": "1"},
@@ -762,6 +789,47 @@ def main():
         sys.exit(3)
     if world > 1:
         dist.destroy_process_group()
+
+
+DUMP_ROWS = 1 << 20             # table rows sampled by --dump-outputs (7 float64 columns: 56 MiB at most)
+DUMP_SEED = 0xD0C5
+
+
+def dump_outputs(out_dir: str, table, cap: int, res: dict, rank: int = 0) -> None:
+    """What a caller of the timed path holds after its last step, as out_dir/<name>.npy in float64: the merge
+    result (crdt_result) and the table rows (lt, rank, val, mod) of a fixed, seeded sample of DUMP_ROWS slots —
+    every slot when the table has no more.  64-bit fields are split into their high and low 32-bit halves, so
+    each float64 is exact and two builds can be compared value for value.  Rank r > 0 of a sharded run writes
+    its shard as <name>_rank<r>.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = f"_rank{rank}" if rank else ""
+
+    def halves(x):
+        u = np.asarray(x).astype(np.int64).view(np.uint64)
+        return (u >> np.uint64(32)).astype(np.float64), (u & np.uint64(0xFFFFFFFF)).astype(np.float64)
+
+    def save(name, a):
+        np.save(os.path.join(out_dir, f"{name}{sfx}.npy"), np.asarray(a, dtype=np.float64))
+
+    if cap <= DUMP_ROWS:
+        slots = np.arange(cap, dtype=np.uint32)
+    else:
+        slots = np.unique(np.random.default_rng(DUMP_SEED).integers(0, cap, DUMP_ROWS, dtype=np.int64))
+        slots = slots.astype(np.uint32)
+    lt, rk, val, mod = table.read_rows(slots)
+    save("rows_slot", slots)
+    for name, col in (("rows_lt", lt), ("rows_mod", mod)):
+        hi, lo = halves(col)
+        save(name + "_hi", hi)
+        save(name + "_lo", lo)
+    save("rows_rank", rk)
+    save("rows_val", val)
+    fields = ("status", "n_stored", "exc_changeset", "exc_index", "canonical_lt", "drift_ms", "counter",
+              "n_present", "n_won")
+    vals = np.array([int(res[f]) & ((1 << 64) - 1) for f in fields], dtype=np.uint64).view(np.int64)
+    hi, lo = halves(vals)
+    save("result_hi", hi)                           # (one entry per crdt_result field, in the order above)
+    save("result_lo", lo)
 
 
 def make_workload(args, dev, rank, world, census):

@@ -4,9 +4,10 @@
 set -u
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 export TMPDIR=/tmp
-OUT=gpurun_out/pmc_cfg3
+BENCH_OUT=${BENCH_OUT:-bench_out}      # where the result lines, logs and traces go
+OUT=$BENCH_OUT/pmc_cfg3
 mkdir -p $OUT
-BENCH="bench.py --config cfg3 --steps 1 --warmup 0 --no-cpu --no-census --no-pcie"
+BENCH="bench.py --full --config cfg3 --steps 1 --warmup 0 --no-cpu --no-census --no-pcie"
 i=0
 for grp in "FETCH_SIZE" "WRITE_SIZE"; do
   i=$((i+1))

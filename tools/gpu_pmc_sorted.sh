@@ -3,9 +3,10 @@
 set -u
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 export TMPDIR=/tmp
-OUT=gpurun_out/pmc_sorted
+BENCH_OUT=${BENCH_OUT:-bench_out}      # where the result lines, logs and traces go
+OUT=$BENCH_OUT/pmc_sorted
 mkdir -p $OUT
-BENCH="bench.py --steps 1 --warmup 0 --no-cpu --no-census --path sorted --records 250000000 --replicas 256 $*"
+BENCH="bench.py --full --steps 1 --warmup 0 --no-cpu --no-census --path sorted --records 250000000 --replicas 256 $*"
 i=0
 for grp in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_INSTS_VALU SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_INSTS_VMEM" \
            "FETCH_SIZE" "WRITE_SIZE" "SQ_WAIT_ANY SQ_INSTS_SALU SQ_ACTIVE_INST_LDS SQ_INST_CYCLES_VMEM SQ_LDS_IDX_ACTIVE"; do

@@ -3,19 +3,20 @@
 # tools/gpu_pmc_write_ab.sh "VAR=value" (one --pmc pass of its own run)
 set -u
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
-mkdir -p gpurun_out
+BENCH_OUT=${BENCH_OUT:-bench_out}      # where the result lines, logs and traces go
+mkdir -p $BENCH_OUT
 export TMPDIR=/tmp
 tag=$(echo "$1" | tr '=,' '__')
 env "$1" true || exit 2
 export "$1"
-timeout -s KILL 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d gpurun_out/pmcw_$tag -o run -- python3 bench.py --steps 2 --warmup 1 --no-cpu --no-census --no-pcie > gpurun_out/pmcw_$tag.log 2>&1
-rc=$?; echo "[write $tag] exit $rc"; [ $rc -eq 0 ] || { tail -5 gpurun_out/pmcw_$tag.log; exit $rc; }
-python3 - "$tag" <<'PY'
+timeout -s KILL 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $BENCH_OUT/pmcw_$tag -o run -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu --no-census --no-pcie > $BENCH_OUT/pmcw_$tag.log 2>&1
+rc=$?; echo "[write $tag] exit $rc"; [ $rc -eq 0 ] || { tail -5 $BENCH_OUT/pmcw_$tag.log; exit $rc; }
+python3 - "$tag" "$BENCH_OUT" <<'PY'
 import csv, glob, sys
 from collections import defaultdict
-tag = sys.argv[1]
+tag, out = sys.argv[1], sys.argv[2]
 per = defaultdict(float)
-for f in glob.glob(f"gpurun_out/pmcw_{tag}/**/*counter_collection.csv", recursive=True):
+for f in glob.glob(f"{out}/pmcw_{tag}/**/*counter_collection.csv", recursive=True):
     for r in csv.DictReader(open(f)):
         n = r.get("Kernel_Name", "")
         if r.get("Counter_Name") == "WRITE_SIZE" and "::k_part" in n:

@@ -4,9 +4,10 @@
 set -u
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 export TMPDIR=/tmp
-OUT=gpurun_out/prof_r1
+BENCH_OUT=${BENCH_OUT:-bench_out}      # where the result lines, logs and traces go
+OUT=$BENCH_OUT/prof_r1
 mkdir -p $OUT
-BENCH="bench.py --steps 2 --warmup 1 --no-cpu --no-census $*"
+BENCH="bench.py --full --steps 2 --warmup 1 --no-cpu --no-census $*"
 stop_on() { case "$1" in 0) ;; 124|137|134|139) echo "[$2] exit $1 -> stop"; exit $1 ;; *) echo "[$2] exit $1" ;; esac; }
 timeout -k 10 60 rocprofv3 -L > $OUT/counters.txt 2>&1; stop_on $? list
 grep -o -E "\b(FETCH_SIZE|WRITE_SIZE|TCC_EA0_RDREQ(_32B)?(_sum)?|TCC_EA0_WRREQ(_64B)?(_sum)?|TCC_HIT(_sum)?|TCC_MISS(_sum)?)\b" $OUT/counters.txt | sort -u > $OUT/counters_found.txt
