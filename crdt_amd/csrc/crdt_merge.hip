@@ -143,6 +143,8 @@ struct Misc {
                                      // its gather row (0: none) — every rank fails the call with it
     unsigned long long fr_cmax;      // k_scan<.., kFrame>: max of the records' lt & 0xFFFF (the compact frame,
                                      // sorted_path.inc PackFrame::cb)
+    unsigned long long hot_n;        // k_hot_count: the records k_scan counted into its hot bins, every changeset's
+    unsigned long long hot_spare;    // (keeps the size a multiple of 16 B)
     unsigned long long present[kCounterSlots];
     unsigned long long won[kCounterSlots];
 };                             // size a multiple of 16 B: hipMemsetAsync zeroes it with one fill
@@ -248,6 +250,10 @@ __host__ __device__ inline uint32_t km_digit(KeyMap m, uint32_t k, uint32_t shif
     return ((((k & ((1u << m.gsh) - 1u)) << m.dsh) | ((k >> m.gsh) >> shift)) & 255u);
 }
 
+constexpr uint32_t kHotShift = 12;               // a hot bin is one final bucket (sorted_path.inc kSBits)
+constexpr uint32_t kHotProbe = 15;               // default of CRDT_HOT_PROBE (crdt_ctx::hot_probe)
+constexpr uint32_t kHotMax = 256;                // at most the final buckets of level-1 digit 0
+
 struct ScanHist {
     const uint32_t* key;
     const uint32_t* ptb;        // [R + 1] first partition tile of changeset j
@@ -257,23 +263,55 @@ struct ScanHist {
     KeyMap km{0u, 8u};
     uint32_t htile = kHistSub * kTile;      // level-1 tile (records): the step's 28672, or 14336 (two per step)
 };
+// kHot (one ctx, two levels): the records of the first `hot` final buckets (key >> 12 < hot) count into a second
+// table hhist[tile][256] (bin = key >> 12, the bins >= hot stay zero) and not into digit 0 of hist — the hot-bucket
+// level 1 of the compact order-free form (sorted_path.inc HotL1); every other form folds them back (k_hot_fold)
+struct ScanHot {
+    uint32_t hot = 0;
+    uint32_t* hhist = nullptr;
+};
+
+// misc->hot_n = the records in the hot bins of every tile (k_scan's ScanHot table), for the host's choice of the
+// form: a pass of its own over the bins < hot, one atomic per workgroup.  (Counted inside the scan — one atomic
+// per workgroup step on this one address — the scan took 4.6 ms instead of 2.3 at 1B records.)
+__global__ __launch_bounds__(1024) void k_hot_count(const uint32_t* __restrict__ hhist, uint64_t tiles, uint32_t hot,
+                                                    Misc* __restrict__ misc)
+{
+    __shared__ unsigned long long s_sum[16];
+    unsigned long long n = 0;
+    const uint64_t words = tiles * 256;
+    for (uint64_t x = (uint64_t)blockIdx.x * 1024 + threadIdx.x; x < words; x += (uint64_t)gridDim.x * 1024)
+        if ((x & 255u) < hot) n += hhist[x];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) n += __shfl_xor(n, off, 64);
+    if ((threadIdx.x & 63) == 0) s_sum[threadIdx.x >> 6] = n;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 1; k < 16; ++k) n += s_sum[k];
+        if (n) atomicAdd(&misc->hot_n, n);
+    }
+}
 
 // kVec: a thread's records are 4 groups of 4 consecutive ones (lt read with two 16-B loads per
 // group, keys with one) instead of 16 strided ones; every per-tile result is order-free.
-template <bool kEager, bool kMillis, bool kFrame, bool kHist, bool kVec>
+template <bool kEager, bool kMillis, bool kFrame, bool kHist, bool kVec, bool kHot = false>
 __device__ __forceinline__ void scan_body(
     const int64_t* __restrict__ lt, const uint32_t* __restrict__ rank,
     const int64_t* __restrict__ millis, const uint64_t* __restrict__ offs,
     const uint32_t* __restrict__ tstart, uint32_t jbase, int64_t c0,
     int64_t wall, uint32_t local_rank,
-    int64_t* __restrict__ T, Misc* __restrict__ misc, uint32_t* __restrict__ cand_tile, ScanHist sh, bool jx)
+    int64_t* __restrict__ T, Misc* __restrict__ misc, uint32_t* __restrict__ cand_tile, ScanHist sh, bool jx,
+    ScanHot ho = ScanHot{})
 {
     // (kFrame without kEager: the lt frame only — the host declared a rank bound, crdt_set_rank_bound)
     __shared__ int64_t s_max[kScanThreads / 64];
     __shared__ int s_flag[kScanThreads / 64];
     __shared__ unsigned long long s_fr[kFrame ? 5 * (kScanThreads / 64) : 1];
-    __shared__ uint32_t s_h[kHist ? 512 : 1];
+    // per level-1 tile of the step 256 bins; kHot: 256 ordinary bins, then the 256 hot ones
+    constexpr uint32_t kBins = kHot ? 512u : 256u;
+    __shared__ uint32_t s_h[kHist ? 2 * kBins : 1];
     static_assert(!kHist || kScanThreads == 256, "one histogram bin per thread");
+    static_assert(!kHot || kHist, "hot bins: beside the fused histogram");
     // jx (the step-major grid): blockIdx.x is the changeset and blockIdx.y the step, so the workgroups run every
     // changeset's first steps before any changeset's last (shorter) one — fewer, shorter tails when a batch is only
     // a few workgroup rounds deep (cfg3: 4 steps of up to 7 tiles per changeset on ~1024 resident workgroups)
@@ -285,8 +323,8 @@ __device__ __forceinline__ void scan_body(
     const uint32_t ustride = jx ? gridDim.y : gridDim.x;
     for (uint32_t u = jx ? blockIdx.y : blockIdx.x; u * kStep < nt; u += ustride) {
       if (kHist) {
-        s_h[threadIdx.x] = 0;
-        s_h[256 + threadIdx.x] = 0;
+#pragma unroll
+        for (uint32_t x = 0; x < (kHist ? 2 * kBins : 0u); x += 256) s_h[kHist ? x + threadIdx.x : 0] = 0;
         __syncthreads();
       }
       const uint32_t te = std::min<uint32_t>(u * kStep + kStep, nt);
@@ -346,8 +384,9 @@ __device__ __forceinline__ void scan_body(
                 // the record's level-1 tile of the step: the same for the whole workgroup at a given q
                 // (its group / stride base decides; the thread offset stays below the 1024 / 256 grain)
                 const uint32_t gb = kVec ? (uint32_t)(q >> 2) * (4u * kScanThreads) : (uint32_t)q * kScanThreads;
-                digit_count(s_h + (tb + gb >= sh.htile ? 256u : 0u), km_digit(sh.km, k, sh.shift),
-                            (k >> sh.km.gsh) < sh.cap, lane);
+                uint32_t dg = km_digit(sh.km, k, sh.shift);
+                if (kHot) dg = (k >> kHotShift) < ho.hot ? 256u + (k >> kHotShift) : dg;
+                digit_count(s_h + (tb + gb >= sh.htile ? kBins : 0u), dg, (k >> sh.km.gsh) < sh.cap, lane);
             }
         }
         // rank / millis matter only for records above C0 (the only ones recv() can raise on)
@@ -426,8 +465,12 @@ __device__ __forceinline__ void scan_body(
         const uint32_t np = sh.ptb[j + 1] - sh.ptb[j];                  // the changeset's level-1 tiles
         const uint32_t per = sh.htile < kHistSub * kTile ? 2u : 1u;
         for (uint32_t h = 0; h < per; ++h)
-            if (u * per + h < np)
-                sh.hist[(uint64_t)(sh.ptb[j] + u * per + h) * 256 + threadIdx.x] = s_h[h * 256 + threadIdx.x];
+            if (u * per + h < np) {
+                sh.hist[(uint64_t)(sh.ptb[j] + u * per + h) * 256 + threadIdx.x] = s_h[h * kBins + threadIdx.x];
+                if (kHot)
+                    ho.hhist[(uint64_t)(sh.ptb[j] + u * per + h) * 256 + threadIdx.x] =
+                        s_h[kHot ? h * kBins + 256 + threadIdx.x : 0];
+            }
       }
     }
 }
@@ -442,6 +485,19 @@ __global__ __launch_bounds__(kScanThreads) void k_scan(
 {
     scan_body<kEager, kMillis, kFrame, kHist, kVec>(lt, rank, millis, offs, tstart, jbase, c0, wall, local_rank, T, misc,
                                                     cand_tile, sh, jx);
+}
+
+// the fused histogram with hot bins (ScanHot): the one-ctx scan of a two-level table
+template <bool kVec>
+__global__ __launch_bounds__(kScanThreads) void k_scan(
+    const int64_t* __restrict__ lt, const uint32_t* __restrict__ rank,
+    const int64_t* __restrict__ millis, const uint64_t* __restrict__ offs,
+    const uint32_t* __restrict__ tstart, uint32_t jbase, int64_t c0,
+    int64_t wall, uint32_t local_rank,
+    int64_t* __restrict__ T, Misc* __restrict__ misc, uint32_t* __restrict__ cand_tile, ScanHist sh, bool jx, ScanHot ho)
+{
+    scan_body<false, true, true, true, kVec, true>(lt, rank, millis, offs, tstart, jbase, c0, wall, local_rank, T, misc,
+                                                   cand_tile, sh, jx, ho);
 }
 
 // M_j = max of changeset j's tile maxima (INT64_MIN when empty).  One block per changeset
@@ -1713,6 +1769,21 @@ struct crdt_ctx {
                                     // 0 off, 1 auto = from 64 changesets, 2 always)
     bool last_combined = false;
     uint32_t sparse_t = 2048;       // CRDT_SPARSE_T: packed resolve buckets of fewer records read only touched rows
+    // CRDT_HOT_BUCKETS=H (0: off): the compact order-free form's level 1 writes the records of the first H final
+    // buckets (keys < H * 4096) straight into their final bucket (sorted_path.inc HotL1): no level 2 for them
+    uint32_t hot_buckets = 256;
+    uint32_t hot_share = 5;         // CRDT_HOT_SHARE (percent): ... only when the scan counted at least this share of
+                                    // the records into the hot bins (uniform keys: the extra digits cost, nothing won)
+    // a merge whose scan counted the hot bins and did not take them (another form, or too small a share) pays for
+    // them in the scan (uniform keys at 1B records: +0.14 ms) and for the fold-back: the scans of the next
+    // hot_probe merges on this ctx count the plain histogram, then one probes again (as scan_eager follows the
+    // previous call).  CRDT_HOT_PROBE=n (default 15; 0: every scan counts them, for A/B runs)
+    uint32_t hot_probe = kHotProbe;
+    uint32_t hot_skip = 0;
+    uint32_t hist1_hot = 0;         // hot bins this plan's scan counted apart (p_hist1h; 0: none / folded back)
+    bool last_hot_direct = false;   // the last sorted apply took the hot-bucket level 1
+    DBuf<uint32_t> p_hist1h, p_toffh, p_dstarth;   // hot tile histogram (the scan's), tile offsets, bucket starts
+    DBuf<uint64_t> p_l1begh;        // the hot starts in 64 bits; [256] = the hot total (level 1's first position)
     int route_l1 = 1;               // CRDT_ROUTE_L1=0: sharded order-free merges route records, owners partition;
                                     // 2: route_l1 always with the sender-side head fold; 3: folding every digit
     bool rl1_call_head = false;     // this call's route_l1 folds the owners' leading level-1 digits (the Zipf head)
@@ -2014,6 +2085,7 @@ int phase_scan(crdt_ctx* c, const crdt_batch* home, int64_t wall, long long* d_m
     c->fused = false;
     c->resolved = false;
     c->hist1_fused = false;
+    c->hist1_hot = 0;
     int st = validate_batch(home);
     if (st) return st;
     const uint32_t R = home->n_changesets;
@@ -2052,6 +2124,18 @@ int phase_scan(crdt_ctx* c, const crdt_batch* home, int64_t wall, long long* d_m
         c->hist1_key = home->key_id;
         c->hist1_shift = rhist || c->cap > (1ull << 20) ? 20u : (uint32_t)kSBits;
     }
+    // a two-level table on one ctx: the hot bins beside the histogram (the form is not known yet: apply_sorted
+    // takes them or folds them back)
+    uint32_t hot = hist && c->cap > (1ull << 20) ? std::min<uint32_t>(c->hot_buckets, kHotMax) : 0u;
+    if (hot && c->hot_skip) {
+        --c->hot_skip;
+        hot = 0;
+    }
+    if (hot) {
+        HIPALLOC(c->p_hist1h.ensure(c->plan_ptiles * kDigits));
+        c->hist1_hot = hot;
+    }
+    const ScanHot shot{hot, c->p_hist1h.p};
     ScanHist shr{home->key_id, c->d_ptb, c->cap, 20u, c->p_hist1.p};
     shr.htile = l1_plan_tile(c);
     ScanHist shist{home->key_id, c->d_ptb, c->cap, c->hist1_shift, c->p_hist1.p};
@@ -2075,6 +2159,14 @@ int phase_scan(crdt_ctx* c, const crdt_batch* home, int64_t wall, long long* d_m
                 k_scan<true, false, true, true, true><<<gdh, kScanThreads, 0, c->stream>>>(
                     cols.lt, cols.rank, nullptr, c->d_offs, c->d_tstart, jb, c->canonical, wall,
                     c->local_rank, c->d_T.p, c->d_misc, c->d_candtile.p, shr, jx);
+            else if (hist && hot && !(c->form_off & kFormNoVecScan))
+                k_scan<true><<<gdh, kScanThreads, 0, c->stream>>>(
+                    cols.lt, cols.rank, cols.millis, c->d_offs, c->d_tstart, jb, c->canonical, wall,
+                    c->local_rank, c->d_T.p, c->d_misc, c->d_candtile.p, shist, jx, shot);
+            else if (hist && hot)
+                k_scan<false><<<gdh, kScanThreads, 0, c->stream>>>(
+                    cols.lt, cols.rank, cols.millis, c->d_offs, c->d_tstart, jb, c->canonical, wall,
+                    c->local_rank, c->d_T.p, c->d_misc, c->d_candtile.p, shist, jx, shot);
             else if (hist && !(c->form_off & kFormNoVecScan))
                 k_scan<false, true, true, true, true><<<gdh, kScanThreads, 0, c->stream>>>(
                     cols.lt, cols.rank, cols.millis, c->d_offs, c->d_tstart, jb, c->canonical, wall,
@@ -2109,6 +2201,8 @@ int phase_scan(crdt_ctx* c, const crdt_batch* home, int64_t wall, long long* d_m
                     cols.lt, cols.rank, cols.millis, c->d_offs, c->d_tstart, jb, c->canonical, wall,
                     c->local_rank, c->d_T.p, c->d_misc, c->d_candtile.p, ScanHist{}, jx);
         }
+        if (hot)
+            k_hot_count<<<64, 1024, 0, c->stream>>>(c->p_hist1h.p, c->plan_ptiles, hot, c->d_misc);
         if (!c->fused)
             k_tmax<<<std::min<uint32_t>(R, 4096), 256, 0, c->stream>>>(c->d_T.p, c->d_tstart, R, d_maxima);
         HIPCHK(hipGetLastError());
@@ -2466,6 +2560,7 @@ int apply_sorted(crdt_ctx* c, const Cols& cols, const Segs& sg, int64_t wall, co
     c->last_packed = pk;
     c->key_end_valid = true;                 // k_bucket_items bounds the rows every window writes
     c->last_hist1_fused = false;
+    c->last_hot_direct = false;
     c->sorted_phases = false;
     // final records with a 1-B key column when the packed key leaves 4 bits free (two levels)
     const bool k8 = pk && two && pf.key4 && !(c->form_off & kFormNoKey8);
@@ -2586,7 +2681,7 @@ int apply_sorted(crdt_ctx* c, const Cols& cols, const Segs& sg, int64_t wall, co
         HIPALLOC(c->p_tseg.ensure(ntm));
         k_seg_index<<<std::min<uint32_t>(grid_for(nt1, 256), 4096), 256, 0, c->stream>>>(d_tb1, nseg, nt1, c->p_tseg.p);
         const TileMap tm1{d_beg, d_end, d_tb1, c->p_tseg.p, d_sj, nseg, l1t};
-        const ScanMap sm1{reinterpret_cast<const uint32_t*>(c->p_plan.p + tail),
+        const ScanMap sm1z{reinterpret_cast<const uint32_t*>(c->p_plan.p + tail),
                           reinterpret_cast<const uint32_t*>(c->p_plan.p + tail + 1), c->p_plan.p + tail + 2, 1};
         if (two) HIPALLOC(c->p_l1beg.ensure(kDigits + 1));
         // level-1 histogram: counted by the scan (then only the changesets >= stop are cleared)
@@ -2596,6 +2691,28 @@ int apply_sorted(crdt_ctx* c, const Cols& cols, const Segs& sg, int64_t wall, co
                         cols.key == c->hist1_key && c->hist1_shift == shift1 && nt1 == c->plan_ptiles &&
                         l1t == l1_plan_tile(c);
         const uint32_t* hist1 = h1 ? c->p_hist1.p : c->p_hist.p;
+        // the hot bins the scan counted apart: the compact order-free form of two levels takes them as level-1
+        // digits of their own (HotL1); any other form gets them back in digit 0 first
+        const uint32_t hb = h1 ? c->hist1_hot : 0u;
+        const uint64_t hot_n = hb && pk ? std::min<uint64_t>(c->h_misc->hot_n, nw) : 0;   // (read with the frame)
+        const bool hotp = hb && cmp && !ord && !em && two && !c->has_comm && hot_n * 100 >= (uint64_t)c->hot_share * nw;
+        if (hb && !hotp) {
+            k_hot_fold<<<std::min<uint32_t>(nt1, 1024u), 64, 0, c->stream>>>(c->p_hist1.p, c->p_hist1h.p, nt1);
+            c->hist1_hot = 0;
+            c->hot_skip = c->hot_probe;
+        }
+        c->last_hot_direct = hotp;
+        if (hotp) {       // hot digits first: their scan from position 0, then the ordinary one from the hot total
+            HIPALLOC(c->p_toffh.ensure((size_t)nt1 * kDigits));
+            HIPALLOC(c->p_dstarth.ensure(kDigits + 1));
+            HIPALLOC(c->p_l1begh.ensure(kDigits + 1));
+            HIPALLOC(c->p2_rec.ensure(rec_units));     // level 1 writes the hot records there
+            k_hist_trim<<<256, 256, 0, c->stream>>>(c->p_hist1h.p, c->d_ptb, R, c->d_misc);
+            k_scan_part<<<nc1, 256, 0, c->stream>>>(c->p_hist1h.p, sm1z, c->p_part.p);
+            k_scan_seg<<<1, 256, 0, c->stream>>>(c->p_part.p, sm1z, c->p_choff.p, c->p_dstarth.p, c->p_l1begh.p);
+            k_scan_tiles<<<nc1, 256, 0, c->stream>>>(c->p_hist1h.p, c->p_choff.p, sm1z, c->p_dstarth.p, c->p_toffh.p);
+        }
+        const ScanMap sm1 = hotp ? ScanMap{sm1z.tbase, sm1z.cbase, c->p_l1begh.p + kDigits, 1} : sm1z;
         if (h1)
             k_hist_trim<<<256, 256, 0, c->stream>>>(c->p_hist1.p, c->d_ptb, R, c->d_misc);
         else
@@ -2622,6 +2739,11 @@ int apply_sorted(crdt_ctx* c, const Cols& cols, const Segs& sg, int64_t wall, co
                 <<<xcd_grid(nt1, c->xcd_map), kPThreads, 0, c->stream>>>(
                 cols.key, cols.lt, cols.rank, cols.val, tm1, jb, c->d_misc, c->cap, shift1, c->p_toff.p, p1r,
                 p1k, xper1, pf, rev1 ? hist1 : nullptr, c->f_pos1.p, hist1);
+        else if (hotp)          // the compact form with hot buckets: their records go to p2 in this pass
+            k_part_scatter1<kL1Items><<<xcd_grid(nt1, c->xcd_map), kPThreads, 0, c->stream>>>(
+                cols.key, cols.lt, cols.rank, cols.val, tm1, jb, c->d_misc, c->cap, shift1, c->p_toff.p, p1r,
+                p1k, xper1, pf, rev1 ? hist1 : nullptr,
+                HotL1{hb, c->p_toffh.p, rev1 ? c->p_hist1h.p : nullptr, c->p2_rec.p});
         else if (cmp)           // the compact form: 12-B records + the 1-B level-2 digit column
             k_part_scatter1<true, false, true, kL1Items, true, true, false, true>
                 <<<xcd_grid(nt1, c->xcd_map), kPThreads, 0, c->stream>>>(
@@ -2715,10 +2837,15 @@ int apply_sorted(crdt_ctx* c, const Cols& cols, const Segs& sg, int64_t wall, co
             k_scan_part<<<nc2, 256, 0, c->stream>>>(h2p, sm2, c->p_part.p);
             k_scan_seg<<<kDigits, 256, 0, c->stream>>>(c->p_part.p, sm2, c->p_choff.p, c->p_dstart2.p, nullptr);
             k_scan_tiles<<<nc2, 256, 0, c->stream>>>(h2p, c->p_choff.p, sm2, c->p_dstart2.p, t2p);
+            // the hot buckets were filled by level 1 at [0, hot total): level 2 saw them empty, all starting there
+            if (hotp) k_hot_starts<<<1, 256, 0, c->stream>>>(c->p_dstart2.p, c->p_dstarth.p, hb);
             // (nt2 is an upper bound of the level-2 tiles; the real count is on the device)
             // (the grid and the XCD-contiguous mapping from a tile bound for THIS tile size: a loose
             // bound would leave the upper XCDs' ranges past the last tile, idle)
-            const uint32_t nt2s = (uint32_t)((nw + ts2 - 1) / ts2) + kDigits;
+            // (the hot records are not level 2's: the scan's count of them is of every changeset, so nw - hot_n
+            // still bounds the records level 2 holds)
+            const uint64_t nw2 = hotp ? nw - hot_n : nw;
+            const uint32_t nt2s = (uint32_t)((nw2 + ts2 - 1) / ts2) + kDigits;
             const uint32_t xper2 = c->xcd_map ? (nt2s + kXcds - 1) / kXcds : 0;
             if (ord) {         // changeset order kept in every final bucket; level-2 run offsets kept
                 if (fl) HIPALLOC(c->f_pos2.ensure(nw + 8));
@@ -3228,6 +3355,9 @@ static void read_env_knobs(crdt_ctx* c) {
     }
     if (const char* e = getenv("CRDT_ROUTE_TUNE")) c->route_tune = atoi(e) != 0;
     if (const char* e = getenv("CRDT_SPARSE_T")) c->sparse_t = (uint32_t)std::max(atoi(e), 0);
+    if (const char* e = getenv("CRDT_HOT_BUCKETS")) c->hot_buckets = (uint32_t)std::min(std::max(atoi(e), 0), (int)kHotMax);
+    if (const char* e = getenv("CRDT_HOT_PROBE")) c->hot_probe = (uint32_t)std::min(std::max(atoi(e), 0), 1 << 20);
+    if (const char* e = getenv("CRDT_HOT_SHARE")) c->hot_share = (uint32_t)std::min(std::max(atoi(e), 0), 100);
     if (const char* e = getenv("CRDT_FBACK_CHK")) c->fback_chk = atoi(e) == 4 ? 4 : atoi(e) == 0 ? 0 : 6;
     if (const char* e = getenv("CRDT_HIST_FUSE")) c->hist_fuse = atoi(e) != 0;
     if (const char* e = getenv("CRDT_L1_TILE"))
@@ -3324,6 +3454,7 @@ void crdt_destroy(crdt_ctx* c) {
     c->p1_rec.release(); c->p1_kj.release(); c->p2_rec.release(); c->p2_kj.release();
     for (int i = 0; i < crdt_ctx::kPlaceMax; ++i) { c->pc_rec[i].release(); c->pc_kj[i].release(); }
     for (hipEvent_t e : c->place_ev) if (e) hipEventDestroy(e);
+    c->p_hist1h.release(); c->p_toffh.release(); c->p_dstarth.release(); c->p_l1begh.release();
     c->p_hist.release(); c->p_hist1.release(); c->p_toff.release(); c->p_part.release(); c->p_choff.release();
     c->p_dstart1.release(); c->p_dstart2.release(); c->p_l2map.release();
     c->p_plan.release(); c->p_l1beg.release(); c->h_pplan.release();
@@ -3717,6 +3848,7 @@ int crdt_last_plan(const crdt_ctx* c, uint32_t* flags) {
         if (c->last_combined) f |= CRDT_PLAN_COMBINED;
         if (c->last_route_l1) f |= CRDT_PLAN_ROUTE_L1;
         if (c->last_compact) f |= CRDT_PLAN_COMPACT;
+        if (c->last_hot_direct) f |= CRDT_PLAN_HOT_DIRECT;
     }
     if (c->last_wire_pk) f |= CRDT_PLAN_WIRE_PACKED;
     if (c->last_own_in_place) f |= CRDT_PLAN_OWN_IN_PLACE;

@@ -281,6 +281,28 @@ __global__ __launch_bounds__(256) void k_hist_trim(uint32_t* __restrict__ hist, 
     for (uint64_t x = a + (uint64_t)blockIdx.x * 256 + threadIdx.x; x < b; x += (uint64_t)gridDim.x * 256)
         hist[x] = 0;
 }
+// The scan's hot bins (k_scan's ScanHot) for a form that does not take them: back into digit 0, so that hist is
+// what it is without them.  One wave per tile (grid-stride).
+__global__ __launch_bounds__(64) void k_hot_fold(uint32_t* __restrict__ hist, const uint32_t* __restrict__ hhist,
+                                                 uint32_t tiles)
+{
+    for (uint32_t t = blockIdx.x; t < tiles; t += gridDim.x) {
+        const uint32_t* h = hhist + (uint64_t)t * kDigits;
+        uint32_t s = h[threadIdx.x] + h[64 + threadIdx.x] + h[128 + threadIdx.x] + h[192 + threadIdx.x];
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+        if (threadIdx.x == 0) hist[(uint64_t)t * kDigits] += s;
+    }
+}
+
+// Final bucket starts of the hot buckets (filled by level 1, HotL1): level 2's scan left bstart[b] = the hot total
+// for the b < hot (empty there); their starts are the hot scan's.
+__global__ __launch_bounds__(256) void k_hot_starts(uint32_t* __restrict__ bstart, const uint32_t* __restrict__ hstart,
+                                                    uint32_t hot)
+{
+    if (threadIdx.x < hot) bstart[threadIdx.x] = hstart[threadIdx.x];
+}
+static_assert(kHotShift == (uint32_t)kSBits && kHotMax == kDigits, "a hot bin is a final bucket of level-1 digit 0");
 static_assert(kPTile == (int)kHistSub * kTile && (kPTile / 2) % 1024 == 0,
               "the largest level-1 tile is kHistSub scan tiles; half of it splits on the scan's 1024-record groups");
 static_assert(kDigits == 256, "k_scan<.., kHist> counts 256 digits");
@@ -918,27 +940,81 @@ __global__ __launch_bounds__(kPThreads) void k_part_scatter2_seg(
 // kPT (with kPos, kVec; one window): the positions tile-strided — tile t's at pos_out[t * kPTile + i], i its record
 // inside the tile — so a thread stores its records' positions straight from registers, 8-B / 4-B aligned (four
 // consecutive records, a pair, a single), with no LDS staging pass; k_flags_back_pre<.., kPT> reads them so.
-template <bool kPk, bool kPkIn = false, bool kK16 = false, int kItems = kL1Items, bool kVec = false,
-          bool kDigKj = kK16, bool kPos = false, bool kC = false, bool kPT = false>
-__global__ __launch_bounds__(kPThreads) void k_part_scatter1(
+// kHot (the compact order-free form, two levels, one window; HotL1): the records of the first h.hot final buckets
+// (slot >> 12 < h.hot) take level-1 digits of their own, 256 + (slot >> 12), whose output ranges come first —
+// h.toff[t][b] from the scan of the hot tile histogram h.thist, starting at position 0 — and are written to
+// h.orec, the level-2 record buffer, at those positions: they are in their final bucket after this one pass.  The
+// ordinary digits' positions start at the hot total (level 2 writes nothing below it) and digit 0 holds only its
+// slots >= h.hot * 4096.  Hot records write no digit column.
+struct HotL1 {
+    uint32_t hot = 0;                  // hot final buckets (<= 256)
+    const uint32_t* toff = nullptr;    // [tiles][256] first position of the tile's records of hot bucket b
+    const uint32_t* thist = nullptr;   // [tiles][256] their counts
+    void* orec = nullptr;              // the level-2 record buffer
+};
+
+// exclusive scan over threads 0..511 (8 waves; every thread of the workgroup calls it); *total = the sum
+__device__ inline uint32_t scan512_excl(uint32_t v, uint32_t* s_w /*[8]*/, uint32_t* total) {
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    uint32_t inc = v;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const uint32_t u = __shfl_up(inc, off, 64);
+        if (lane >= off) inc += u;
+    }
+    if (tid < 512 && lane == 63) s_w[w] = inc;
+    __syncthreads();
+    uint32_t x = lane < 8 ? s_w[lane] : 0u;              // the 8 wave sums, scanned by every wave's first lanes
+#pragma unroll
+    for (int off = 1; off < 8; off <<= 1) {
+        const uint32_t u = __shfl_up(x, off, 64);
+        if (lane >= off) x += u;
+    }
+    const int wu = __builtin_amdgcn_readfirstlane(w);
+    *total = (uint32_t)__builtin_amdgcn_readlane((int)x, 7);
+    const uint32_t wp = wu == 0 ? 0u : wu <= 8 ? (uint32_t)__builtin_amdgcn_readlane((int)x, wu - 1) : *total;
+    return wp + inc - v;
+}
+
+// digit_count (crdt_merge.hip) with the wave's shared values read across lanes into scalars and the lane's rank
+// inside the matching lanes counted by mbcnt: no lane id or lane mask kept in vector registers (the hot-bucket
+// level 1 runs at its register cap).  The first lane of the match mask is the first active lane.
+__device__ inline uint32_t digit_count_s(uint32_t* bins, uint32_t d, bool act) {
+    const unsigned long long a = __ballot(act);
+    if (!a) return 0;
+    const int L = __ffsll((long long)a) - 1;
+    const uint32_t d0 = (uint32_t)__builtin_amdgcn_readlane((int)d, L);
+    const bool same = act && d == d0;
+    const unsigned long long m = __ballot(same);
+    const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+    uint32_t base = 0;
+    if (same && below == 0) base = atomicAdd(&bins[d0], (uint32_t)__popcll(m));
+    base = (uint32_t)__builtin_amdgcn_readlane((int)base, L);
+    if (same) return base + below;
+    return act ? atomicAdd(&bins[d], 1u) : 0u;
+}
+
+template <bool kPk, bool kPkIn, bool kK16, int kItems, bool kVec, bool kDigKj, bool kPos, bool kC, bool kPT, bool kHot>
+__device__ __forceinline__ void part_scatter1_body(
     const uint32_t* __restrict__ keyw, const int64_t* __restrict__ lt, const uint32_t* __restrict__ rank,
     const uint32_t* __restrict__ val, TileMap tm, uint32_t jbase, Misc* __restrict__ misc, uint64_t cap,
     uint32_t shift, const uint32_t* __restrict__ toff, void* __restrict__ orec, void* __restrict__ okj,
     uint32_t xper, PackFrame pf, const uint32_t* __restrict__ thist,
-    uint16_t* __restrict__ pos_out = nullptr, const uint32_t* __restrict__ phist = nullptr,
-    KeyMap km = KeyMap{0u, 8u})
+    uint16_t* __restrict__ pos_out, const uint32_t* __restrict__ phist, KeyMap km, HotL1 hl)
 {
     static_assert(!kK16 || kPk, "2-B key column: packed records only");
     static_assert(!kDigKj || kK16, "digit beside the 16-bit key: 2-B key columns only");
     static_assert(!kC || (kK16 && kDigKj && !kPkIn), "compact: one ctx's packed forms");
     static_assert(!kPT || (kPos && kVec && (kPThreads * kItems) % 8 == 0), "tile-strided positions: kVec groups");
+    static_assert(!kHot || (kC && !kPos && kPThreads >= 512), "hot buckets: the compact order-free form");
     constexpr int kW = kPk ? 3 : 4;
     constexpr int kI = kItems;                            // records per thread per sub-tile
     constexpr int kS = kPThreads * kI;                    // records per LDS sub-tile
-    __shared__ uint32_t cur[kDigits];
-    __shared__ uint32_t cnt[kDigits];
-    __shared__ uint32_t dst[kDigits + 1];
-    __shared__ uint32_t s_w[4];
+    constexpr int kND = kHot ? 2 * (int)kDigits : (int)kDigits;   // digits: the ordinary 256 (+ 256 hot ones)
+    __shared__ uint32_t cur[kND];
+    __shared__ uint32_t cnt[kND];
+    __shared__ uint32_t dst[kND + 1];
+    __shared__ uint32_t s_w[kHot ? 8 : 4];
     __shared__ u32x4 s_rec[kPk ? 1 : kS];             // wide: 112 KB (7 per thread)
     __shared__ uint32_t s_pay[kPk ? kW : 1][kPk ? kS : 1];   // packed: 84 KB
     __shared__ uint32_t s_kj[kS];                     //  28 KB
@@ -960,6 +1036,9 @@ __global__ __launch_bounds__(kPThreads) void k_part_scatter1(
     const bool rev = thist && (t & 1u);
     if (tid < (int)kDigits)
         cur[tid] = toff[(uint64_t)t * kDigits + tid] + (rev ? thist[(uint64_t)t * kDigits + tid] : 0u);
+    else if (kHot && tid < kND)
+        cur[tid] = hl.toff[(uint64_t)t * kDigits + tid - kDigits] +
+                   (rev ? hl.thist[(uint64_t)t * kDigits + tid - kDigits] : 0u);
     if constexpr (kPos) {                                // (a barrier precedes every read of s_t0)
         uint32_t all;
         const uint32_t hv = tid < (int)kDigits ? phist[(uint64_t)t * kDigits + tid] : 0u;
@@ -1042,7 +1121,7 @@ __global__ __launch_bounds__(kPThreads) void k_part_scatter1(
     };
     load_sub(0);
     for (uint32_t sb = 0; sb < len; sb += kS) {
-        if (tid < (int)kDigits) cnt[tid] = 0;
+        if (tid < kND) cnt[tid] = 0;
         uint32_t rec[kI][kW];
         uint32_t k[kI], d[kI], slot[kI];
         bool act[kI];
@@ -1075,31 +1154,33 @@ __global__ __launch_bounds__(kPThreads) void k_part_scatter1(
             bad |= act[q] && sl >= cap;
             act[q] = act[q] && sl < cap;
             d[q] = km_digit(km, k[q], shift);
+            if (kHot) d[q] = (sl >> kSBits) < hl.hot ? kDigits + (sl >> kSBits) : d[q];
             if (kC) {
                 rec[q][1] |= (sl & 0xFFFFFu) << (kCKeyShift - 32);
                 k[q] = (sl >> 12) & 0xFFu;
+                if (kHot) k[q] |= d[q] << 16;            // (the staged word already: d[] is not kept in registers)
             } else if (kK16) {
                 rec[q][1] |= (sl & 15u) << 28;
                 k[q] = (sl >> 4) & 0xFFFFu;
             } else {
                 k[q] = (sl & kKeyLoMask) | ((jw - jbase) << kJShift);
             }
-            slot[q] = digit_count(cnt, d[q], act[q], lane);
+            slot[q] = kHot ? digit_count_s(cnt, d[q], act[q]) : digit_count(cnt, d[q], act[q], lane);
         }
         __syncthreads();
         uint32_t all;
-        const uint32_t tv = tid < (int)kDigits ? cnt[tid] : 0u;
-        const uint32_t ex = scan256_excl(tv, s_w, &all);
-        if (tid < (int)kDigits) {
+        const uint32_t tv = tid < kND ? cnt[tid] : 0u;
+        const uint32_t ex = kHot ? scan512_excl(tv, s_w, &all) : scan256_excl(tv, s_w, &all);
+        if (tid < kND) {
             dst[tid] = ex;
-            if (tid == kDigits - 1) dst[kDigits] = ex + tv;
+            if (tid == kND - 1) dst[kND] = ex + tv;
             if (rev) cur[tid] -= tv;                     // this sub-tile's chunk ends where the last began
         }
         __syncthreads();
 #pragma unroll
         for (int q = 0; q < kI; ++q) {
             if (act[q]) {
-                const uint32_t pos = dst[d[q]] + slot[q];
+                const uint32_t pos = dst[kHot ? k[q] >> 16 : d[q]] + slot[q];
                 if constexpr (kPk) {
 #pragma unroll
                     for (int x = 0; x < kW; ++x) s_pay[x][pos] = rec[q][x];
@@ -1107,7 +1188,9 @@ __global__ __launch_bounds__(kPThreads) void k_part_scatter1(
                     u32x4 r4; r4.x = rec[q][0]; r4.y = rec[q][1]; r4.z = rec[q][2]; r4.w = rec[q][kW - 1];
                     s_rec[pos] = r4;
                 }
-                if (kDigKj) {
+                if (kHot) {
+                    s_kj[pos] = k[q];
+                } else if (kDigKj) {
                     s_kj[pos] = k[q] | (d[q] << 16);            // one LDS write for key and digit
                 } else {
                     s_kj[pos] = k[q];
@@ -1153,7 +1236,7 @@ __global__ __launch_bounds__(kPThreads) void k_part_scatter1(
             }
         }
         __syncthreads();
-        const uint32_t staged = dst[kDigits];
+        const uint32_t staged = dst[kND];
         if constexpr (kPos && !kPT) {   // the sub-tile's positions: 8 per 16-B store on the aligned body
             const uint32_t ns = std::min<uint32_t>((uint32_t)kS, len - sb);
             uint16_t* __restrict__ po = pos_out + beg + sb;
@@ -1183,20 +1266,53 @@ __global__ __launch_bounds__(kPThreads) void k_part_scatter1(
                     uint32_t o[kW];
 #pragma unroll
                     for (int x = 0; x < kW; ++x) o[x] = s_pay[x][s];
-                    store_payload<kPk>(orec, g, o);
+                    store_payload<kPk>(kHot && dd >= kDigits ? hl.orec : orec, g, o);
                 } else {
                     static_cast<u32x4*>(orec)[g] = s_rec[s];
                 }
+                if (kHot && dd >= kDigits) continue;     // a final record: no digit column
                 if (kC) static_cast<uint8_t*>(okj)[g] = (uint8_t)kw;
                 else if (kK16) static_cast<uint16_t*>(okj)[g] = (uint16_t)kw;
                 else static_cast<uint32_t*>(okj)[g] = kw;
             }
         }
         __syncthreads();
-        if (tid < (int)kDigits && !rev) cur[tid] += dst[tid + 1] - dst[tid];
+        if (tid < kND && !rev) cur[tid] += dst[tid + 1] - dst[tid];
     }
-    if (__any(bad) && lane == 0) atomicOr(&misc->err, 1u);
-    if (kPk && __any(over) && lane == 0) atomicOr(&misc->err, 2u);
+    // (kHot: the first lane from the exec mask here, so that no lane id stays in a register through the loop)
+    const unsigned long long em = kHot ? __ballot(true) : 0ull;
+    const bool l0 = kHot ? __builtin_amdgcn_mbcnt_hi((uint32_t)(em >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)em, 0u)) == 0u
+                         : lane == 0;
+    if (__any(bad) && l0) atomicOr(&misc->err, 1u);
+    if (kPk && __any(over) && l0) atomicOr(&misc->err, 2u);
+}
+
+template <bool kPk, bool kPkIn = false, bool kK16 = false, int kItems = kL1Items, bool kVec = false,
+          bool kDigKj = kK16, bool kPos = false, bool kC = false, bool kPT = false>
+__global__ __launch_bounds__(kPThreads) void k_part_scatter1(
+    const uint32_t* __restrict__ keyw, const int64_t* __restrict__ lt, const uint32_t* __restrict__ rank,
+    const uint32_t* __restrict__ val, TileMap tm, uint32_t jbase, Misc* __restrict__ misc, uint64_t cap,
+    uint32_t shift, const uint32_t* __restrict__ toff, void* __restrict__ orec, void* __restrict__ okj,
+    uint32_t xper, PackFrame pf, const uint32_t* __restrict__ thist,
+    uint16_t* __restrict__ pos_out = nullptr, const uint32_t* __restrict__ phist = nullptr,
+    KeyMap km = KeyMap{0u, 8u})
+{
+    part_scatter1_body<kPk, kPkIn, kK16, kItems, kVec, kDigKj, kPos, kC, kPT, false>(
+        keyw, lt, rank, val, tm, jbase, misc, cap, shift, toff, orec, okj, xper, pf, thist, pos_out, phist, km, HotL1{});
+}
+
+// The compact order-free form with hot buckets (HotL1 above); the same kernel name on purpose: it is the level-1
+// scatter of the merges that take it.
+template <int kItems = kL1Items>
+__global__ __launch_bounds__(kPThreads) void k_part_scatter1(
+    const uint32_t* __restrict__ keyw, const int64_t* __restrict__ lt, const uint32_t* __restrict__ rank,
+    const uint32_t* __restrict__ val, TileMap tm, uint32_t jbase, Misc* __restrict__ misc, uint64_t cap,
+    uint32_t shift, const uint32_t* __restrict__ toff, void* __restrict__ orec, void* __restrict__ okj,
+    uint32_t xper, PackFrame pf, const uint32_t* __restrict__ thist, HotL1 hl)
+{
+    part_scatter1_body<true, false, true, kItems, true, true, false, true, false, true>(
+        keyw, lt, rank, val, tm, jbase, misc, cap, shift, toff, orec, okj, xper, pf, thist, nullptr, nullptr,
+        KeyMap{0u, 8u}, hl);
 }
 
 // ---------------------------------------------------------------------- resolve

@@ -333,10 +333,13 @@ enum crdt_plan_flags {
     CRDT_PLAN_RL1_HEAD = 262144, /* route_l1 folded each owner's first level-1 digit (its 2^20 lowest slots,
                                     the Zipf head) at the sender: one packed maximum per key crossed the
                                     exchange for those keys (comm_path.inc) */
-    CRDT_PLAN_COMPACT = 524288   /* the sorted path's compact form: the records' lt field packed as
+    CRDT_PLAN_COMPACT = 524288,  /* the sorted path's compact form: the records' lt field packed as
                                     (lt >> 16 - min, lt & 0xFFFF) in as many bits as the batch needs, so a record's
                                     whole 20-bit level-1 slot rides in its 64-bit key: 12-B partition records
                                     (sorted_path.inc, PackFrame::cb) */
+    CRDT_PLAN_HOT_DIRECT = 1048576 /* the compact order-free form of a two-level table: level 1 wrote the records of
+                                    the first CRDT_HOT_BUCKETS final buckets (keys < H * 4096) straight into their
+                                    final bucket; they skipped level 2 (sorted_path.inc, HotL1) */
 };
 int crdt_last_plan(const crdt_ctx* ctx, uint32_t* flags);
 
