@@ -57,6 +57,16 @@ class CrdtTiming(ctypes.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+class CrdtExport(ctypes.Structure):
+    _fields_ = [("key_id", ctypes.c_void_p), ("lt", ctypes.c_void_p), ("rank", ctypes.c_void_p),
+                ("val", ctypes.c_void_p), ("mod", ctypes.c_void_p), ("n", ctypes.c_uint64),
+                ("n_live", ctypes.c_uint64), ("mem", ctypes.c_int32), ("device", ctypes.c_int32)]
+
+
+EXPORT_TILE = 2048                         # rows per workgroup of the export's passes (crdt_merge.hip kExTile)
+EXPORT_SCAN_STEP = 1024                    # tile counts its scan takes per loop iteration (kExScanStep)
+EXPORT_COUNT_GRID = 2048                   # workgroups of its count pass, striding over the tiles (kExCountGrid)
+
 # crdt_comm_ops callbacks (include/crdt_merge.h)
 ALL_REDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int32,
                                  ctypes.c_void_p)
@@ -99,6 +109,10 @@ SIGNATURES = {
     "crdt_put_rows": (_INT, [_P, _P, _P, _P, _P, _P, _U64, _I32]),
     "crdt_read_rows": (_INT, [_P, _P, _U64, _P, _P, _P, _P, _I32]),
     "crdt_modified_since": (_INT, [_P, _U64, _I64, _P, _P]),
+    "crdt_export_since": (_INT, [_P, _U64, _I64, _P]),
+    "crdt_export_read": (_INT, [_P, _U64, _U64, _P, _P, _P, _P, _P]),
+    "crdt_export_release": (_INT, [_P]),
+    "crdt_count_since": (_INT, [_P, _U64, _I64, _P, _P]),
     "crdt_clear_rows": (_INT, [_P, _U64, _U64]),
     "crdt_remap_ranks": (_INT, [_P, _U64, _P, _U32]),
     "crdt_put_stamped": (_INT, [_P, _P, _P, _U64, _I64, _I32, _P]),

@@ -211,6 +211,16 @@ class MapCrdt(Crdt):
         modified = self._mod_override.get(kid) or Hlc.fromLogicalTime(int(mod), self.nodeId)
         return Record(hlc, self._values.get(int(val)), modified)
 
+    # ------------------------------------------------------------ views
+    @property
+    def length(self) -> int:                                            # crdt.dart:20 (map.length)
+        """Live records counted on the device (crdt_count_since): no Record is built."""
+        return self._table.count_since(len(self._keys), 0)[1]
+
+    @property
+    def isEmpty(self) -> bool:                                          # crdt.dart:17
+        return self.length == 0
+
     # ------------------------------------------------------------ SPI
     def containsKey(self, key) -> bool:                                 # map_crdt.dart:21
         return self._keys.get(key) is not None
@@ -230,10 +240,10 @@ class MapCrdt(Crdt):
 
     def recordMap(self, modifiedSince: Hlc | None = None) -> dict:      # map_crdt.dart:42-45
         since = modifiedSince.logicalTime if modifiedSince is not None else 0
-        ids = self._table.modified_since(len(self._keys), since)
-        if len(ids) == 0:
+        ex = self._table.export_since(len(self._keys), since)       # one device compaction of all columns
+        if ex.n == 0:
             return {}
-        lt, rank, val, mod = self._table.read_rows(ids)
+        ids, lt, rank, val, mod = ex.columns()
         keys = self._keys.keys
         return {keys[int(i)]: self._make_record(int(i), lt[x], rank[x], val[x], mod[x])
                 for x, i in enumerate(ids)}
@@ -259,11 +269,11 @@ class MapCrdt(Crdt):
         from . import hostlib
         from .crdt_json import _default
         since = modifiedSince.logicalTime if modifiedSince is not None else 0
-        ids = self._table.modified_since(len(self._keys), since)
-        if len(ids) == 0:
+        ex = self._table.export_since(len(self._keys), since)
+        if ex.n == 0:
             self.last_export = "native"
             return "{}"
-        lt, rank, val, _ = self._table.read_rows(ids)
+        ids, lt, rank, val, _ = ex.columns()
         hlc_text = None
         if self._hlc_override:
             pos = {int(k): x for x, k in enumerate(ids.tolist())} if len(self._hlc_override) > 64 else None

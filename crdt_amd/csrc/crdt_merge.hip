@@ -1514,6 +1514,160 @@ __global__ __launch_bounds__(256) void k_ms_write(Table table, uint64_t n, int64
     }
 }
 
+// ---- changeset export (crdt_export_since / crdt_count_since): recordMap(modifiedSince) as five
+// device columns {key_id, lt, rank, val, mod}, ascending by id — the Map a peer's merge() takes
+// (crdt.dart:157-160).  Two passes over tiles of kExTile rows with a scan of the tile counts between
+// them; no workgroup waits on another.  A thread takes rows base + q * 256 + tid, q < kExItems, so a
+// wave-instruction covers 64 consecutive rows and all of a thread's loads are in flight together
+// (rows past n are clamped to row n - 1 and masked, not branched around).
+//   k_ex_count  12 B of every row ({mod_hi, mod_lo, val}: every line of the table once) -> each tile's
+//               selected rows, and the live ones (val != CRDT_NULL_VALUE) summed into words[1]
+//   k_ex_scan   exclusive scan of the tile counts -> offs[nb + 1] (64-bit), total in words[0]
+//   k_ex_write  a tile that selected nothing returns before any row load; another takes each row's
+//               hot and cold half into registers once and stores the five columns at its positions
+constexpr int kExThreads = 256;
+constexpr int kExItems = 8;
+constexpr int kExTile = kExThreads * kExItems;   // 2048 rows: 48 KB of 24-B rows per workgroup
+constexpr int kExScanStep = 1024;                // tile counts k_ex_scan takes per iteration of its loop
+typedef uint32_t u32x3u __attribute__((ext_vector_type(3), aligned(4)));
+
+// A capped grid strides over the tiles and each workgroup sums its live rows (and, for crdt_count_since:
+// counts == nullptr, its selected rows) in a register, so the atomics on words[] are two per workgroup,
+// not two per tile (one per tile measured 0.8 ms at 65536 tiles: same-address atomics serialise).
+constexpr unsigned kExCountGrid = 2048;          // 256 CUs x 8 resident workgroups
+__global__ __launch_bounds__(kExThreads) void k_ex_count(Table table, uint64_t n, int64_t since, uint32_t nb,
+                                                         uint32_t* __restrict__ counts,
+                                                         unsigned long long* __restrict__ words)
+{
+    __shared__ uint32_t s_cl[2][4];              // per wave: selected | live << 16; one buffer per tile parity
+    unsigned long long csum = 0, lsum = 0;       // (thread 0's)
+    uint32_t par = 0;
+    for (uint32_t tile = blockIdx.x; tile < nb; tile += gridDim.x, par ^= 1u) {
+        const uint64_t base = (uint64_t)tile * kExTile;
+        u32x3u v[kExItems];
+#pragma unroll
+        for (int q = 0; q < kExItems; ++q) {
+            const uint64_t i = base + q * kExThreads + threadIdx.x;
+            v[q] = *reinterpret_cast<const u32x3u*>(row_ptr(table, i < n ? i : n - 1) + 12);
+        }
+        uint32_t cl = 0;
+#pragma unroll
+        for (int q = 0; q < kExItems; ++q) {
+            const uint64_t i = base + q * kExThreads + threadIdx.x;
+            const int64_t mod = (int64_t)(((uint64_t)v[q].x << 32) | v[q].y);
+            const bool keep = i < n && !(mod < since);
+            cl += (uint32_t)keep + ((uint32_t)(keep && v[q].z != CRDT_NULL_VALUE) << 16);
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) cl += __shfl_xor(cl, off, 64);
+        if ((threadIdx.x & 63) == 0) s_cl[par][threadIdx.x >> 6] = cl;
+        __syncthreads();                         // (the next tile writes the other buffer)
+        if (threadIdx.x == 0) {
+            cl = s_cl[par][0] + s_cl[par][1] + s_cl[par][2] + s_cl[par][3];
+            if (counts) counts[tile] = cl & 0xFFFFu;
+            else csum += cl & 0xFFFFu;
+            lsum += cl >> 16;
+        }
+    }
+    if (threadIdx.x == 0) {
+        if (csum) atomicAdd(&words[0], csum);
+        if (lsum) atomicAdd(&words[1], lsum);
+    }
+}
+
+__global__ __launch_bounds__(kExScanStep) void k_ex_scan(const uint32_t* __restrict__ counts, uint32_t nb,
+                                                         uint64_t* __restrict__ offs,
+                                                         unsigned long long* __restrict__ words)
+{
+    __shared__ unsigned long long s_wave[16];
+    __shared__ unsigned long long s_carry;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    if (tid == 0) s_carry = 0;
+    __syncthreads();
+    for (uint32_t base = 0; base < nb; base += kExScanStep) {
+        const uint32_t i = base + tid;
+        const unsigned long long v = i < nb ? counts[i] : 0;
+        unsigned long long x = v;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const unsigned long long u = __shfl_up(x, off, 64);
+            if (lane >= off) x += u;
+        }
+        if (lane == 63) s_wave[w] = x;
+        __syncthreads();
+        if (w == 0) {
+            unsigned long long y = lane < 16 ? s_wave[lane] : 0;
+#pragma unroll
+            for (int off = 1; off < 16; off <<= 1) {
+                const unsigned long long u = __shfl_up(y, off, 64);
+                if (lane >= off) y += u;
+            }
+            if (lane < 16) s_wave[lane] = y;
+        }
+        __syncthreads();
+        const unsigned long long pre = (w > 0 ? s_wave[w - 1] : 0) + s_carry;
+        if (i < nb) offs[i] = pre + x - v;
+        __syncthreads();
+        if (tid == 0) s_carry += s_wave[15];
+        __syncthreads();
+    }
+    if (tid == 0) { offs[nb] = s_carry; words[0] = s_carry; }
+}
+
+__global__ __launch_bounds__(kExThreads) void k_ex_write(Table table, uint64_t n, int64_t since,
+                                                         const uint64_t* __restrict__ offs,
+                                                         uint32_t* __restrict__ key, int64_t* __restrict__ lt,
+                                                         uint32_t* __restrict__ rank, uint32_t* __restrict__ val,
+                                                         int64_t* __restrict__ mod)
+{
+    __shared__ uint32_t s_cnt[kExItems * 4];
+    const uint64_t o0 = offs[blockIdx.x];
+    if (offs[blockIdx.x + 1] == o0) return;       // the whole workgroup: nothing selected in this tile
+    const uint64_t base = (uint64_t)blockIdx.x * kExTile;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    uint4 h[kExItems];
+    uint2 x[kExItems];
+#pragma unroll
+    for (int q = 0; q < kExItems; ++q) {
+        const uint64_t i = base + q * kExThreads + threadIdx.x;
+        const uint64_t ic = i < n ? i : n - 1;
+        h[q] = load_hot(table, ic);
+        x[q] = load_cold(table, ic);
+    }
+    uint32_t keep = 0;
+    uint32_t before[kExItems];
+#pragma unroll
+    for (int q = 0; q < kExItems; ++q) {
+        const uint64_t i = base + q * kExThreads + threadIdx.x;
+        const int64_t m = (int64_t)(((uint64_t)h[q].w << 32) | x[q].x);
+        const bool k = i < n && !(m < since);
+        const unsigned long long b = __ballot(k);
+        before[q] = (uint32_t)__popcll(b & ((1ull << lane) - 1));
+        if (lane == 0) s_cnt[q * 4 + w] = (uint32_t)__popcll(b);
+        keep |= (uint32_t)k << q;
+    }
+    __syncthreads();
+    uint32_t run = 0;
+#pragma unroll
+    for (int q = 0; q < kExItems; ++q) {
+        uint32_t pre = run;
+#pragma unroll
+        for (int ww = 0; ww < 4; ++ww) {
+            const uint32_t cnt = s_cnt[q * 4 + ww];
+            pre += ww < w ? cnt : 0u;
+            run += cnt;
+        }
+        if ((keep >> q) & 1u) {
+            const uint64_t pos = o0 + pre + before[q];
+            key[pos] = (uint32_t)(base + q * kExThreads + threadIdx.x);
+            lt[pos] = (int64_t)(((uint64_t)h[q].y << 32) | h[q].x);
+            rank[pos] = h[q].z;
+            val[pos] = x[q].y;
+            mod[pos] = (int64_t)(((uint64_t)h[q].w << 32) | x[q].x);
+        }
+    }
+}
+
 __global__ __launch_bounds__(256) void k_fill_i64(long long* __restrict__ p, uint64_t n, long long v)
 {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1679,6 +1833,14 @@ struct crdt_ctx {
     DBuf<int64_t> s_lt, s_millis, s_mod;
     DBuf<uint8_t> s_flags;
     DBuf<uint32_t> s_out;
+    // crdt_export_since: the changeset view's columns, in buffers of their own (merges and puts on this
+    // ctx reuse the s_* staging, never these), valid until the next export / release / destroy
+    DBuf<uint32_t> x_key, x_rank, x_val, x_counts;
+    DBuf<int64_t> x_lt, x_mod;
+    DBuf<uint64_t> x_offs;
+    DBuf<unsigned long long> x_words;  // [0] selected rows, [1] live ones (k_ex_count / k_ex_scan)
+    bool x_valid = false;              // a view is out (host-side state: crdt_export_read checks it)
+    uint64_t x_n = 0;
     DBuf<long long> d_word;
     DBuf<unsigned long long> d_ibase;
     // per-call plan (set by scan, used by later phases)
@@ -3449,6 +3611,8 @@ void crdt_destroy(crdt_ctx* c) {
     c->d_candkey.release();
     c->s_key.release(); c->s_rank.release(); c->s_val.release(); c->s_lt.release();
     c->s_millis.release(); c->s_mod.release(); c->s_flags.release(); c->s_out.release();
+    c->x_key.release(); c->x_rank.release(); c->x_val.release(); c->x_lt.release(); c->x_mod.release();
+    c->x_counts.release(); c->x_offs.release(); c->x_words.release();
     c->d_word.release();
     c->d_ibase.release();
     c->p1_rec.release(); c->p1_kj.release(); c->p2_rec.release(); c->p2_kj.release();
@@ -3700,6 +3864,122 @@ int crdt_modified_since(crdt_ctx* c, uint64_t n_rows, int64_t since_lt, uint32_t
     HIPCHK(hipStreamSynchronize(c->stream));
     if (total) HIPCHK(hipMemcpy(out_ids, c->s_out.p, total * sizeof(uint32_t), hipMemcpyDeviceToHost));
     *n_out = total;
+    return CRDT_OK;
+}
+
+// ---- changeset export: recordMap(modifiedSince) left on the device (crdt.dart:157-160)
+// The rows the export's passes read.  Rows at or above the high-water mark hold the never-written
+// fill, whose mod 0x8080808080808080 the predicate rejects for every since above it; at or below it
+// (since = INT64_MIN) the fill is selected like any row, so every row is read.
+static uint64_t ex_rows(const crdt_ctx* c, uint64_t n_rows, int64_t since) {
+    constexpr int64_t kFillMod = (int64_t)0x8080808080808080ull;
+    return since > kFillMod ? std::min<uint64_t>(n_rows, c->hw) : n_rows;
+}
+
+static void ex_drop(crdt_ctx* c) {
+    c->x_valid = false;
+    c->x_n = 0;
+    c->x_key.release(); c->x_rank.release(); c->x_val.release(); c->x_lt.release(); c->x_mod.release();
+}
+
+int crdt_count_since(crdt_ctx* c, uint64_t n_rows, int64_t since_lt, uint64_t* n, uint64_t* n_live) {
+    if (!c || !n || !n_live || n_rows > c->cap) return CRDT_E_INVALID;
+    *n = *n_live = 0;
+    const uint64_t rows = ex_rows(c, n_rows, since_lt);
+    if (rows == 0) return CRDT_OK;
+    HIPCHK(hipSetDevice(c->device));
+    HIPALLOC(c->x_words.ensure(2));
+    HIPCHK(hipMemsetAsync(c->x_words.p, 0, 2 * sizeof(unsigned long long), c->stream));
+    const unsigned nb = grid_for(rows, kExTile);
+    k_ex_count<<<std::min(nb, kExCountGrid), kExThreads, 0, c->stream>>>(c->table, rows, since_lt, nb, nullptr,
+                                                                         c->x_words.p);
+    HIPCHK(hipGetLastError());
+    unsigned long long w[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(w, c->x_words.p, sizeof(w), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    *n = w[0];
+    *n_live = w[1];
+    return CRDT_OK;
+}
+
+int crdt_export_since(crdt_ctx* c, uint64_t n_rows, int64_t since_lt, crdt_export* out) {
+    if (!c || !out || n_rows > c->cap) return CRDT_E_INVALID;
+    memset(out, 0, sizeof(*out));
+    out->mem = CRDT_MEM_DEVICE;
+    out->device = c->device;
+    c->x_valid = false;                               // the earlier view ends here, whatever follows
+    c->x_n = 0;
+    const uint64_t rows = ex_rows(c, n_rows, since_lt);
+    if (rows == 0) { c->x_valid = true; return CRDT_OK; }
+    HIPCHK(hipSetDevice(c->device));
+    const unsigned nb = grid_for(rows, kExTile);
+    HIPALLOC(c->x_words.ensure(2));
+    HIPALLOC(c->x_counts.ensure(nb));
+    HIPALLOC(c->x_offs.ensure((size_t)nb + 1));
+    HIPCHK(hipMemsetAsync(c->x_words.p, 0, 2 * sizeof(unsigned long long), c->stream));
+    k_ex_count<<<std::min(nb, kExCountGrid), kExThreads, 0, c->stream>>>(c->table, rows, since_lt, nb,
+                                                                         c->x_counts.p, c->x_words.p);
+    k_ex_scan<<<1, kExScanStep, 0, c->stream>>>(c->x_counts.p, nb, c->x_offs.p, c->x_words.p);
+    HIPCHK(hipGetLastError());
+    unsigned long long w[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(w, c->x_words.p, sizeof(w), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    const uint64_t total = w[0];
+    if (total > rows) return CRDT_E_HIP;              // (never: the counts are of these rows)
+    if (total) {
+        // column buffers for total records: grown to fit, and given back first when they hold over four
+        // times as many (a full export must not pin its gigabytes under the sparse deltas that follow it)
+        auto ex_fit = [](auto& b, uint64_t n) {
+            if (b.p && b.n > 4 * std::max<uint64_t>(n, 1u << 16)) b.release();
+            return b.ensure(n);
+        };
+        hipError_t e = ex_fit(c->x_key, total);
+        if (e == hipSuccess) e = ex_fit(c->x_lt, total);
+        if (e == hipSuccess) e = ex_fit(c->x_rank, total);
+        if (e == hipSuccess) e = ex_fit(c->x_val, total);
+        if (e == hipSuccess) e = ex_fit(c->x_mod, total);
+        if (e != hipSuccess) {
+            ex_drop(c);
+            return e == hipErrorOutOfMemory ? CRDT_E_NOMEM : CRDT_E_HIP;
+        }
+        k_ex_write<<<nb, kExThreads, 0, c->stream>>>(c->table, rows, since_lt, c->x_offs.p, c->x_key.p,
+                                                     c->x_lt.p, c->x_rank.p, c->x_val.p, c->x_mod.p);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(c->stream));      // drained: another ctx's stream may read the columns
+        out->key_id = c->x_key.p;
+        out->lt = c->x_lt.p;
+        out->rank = c->x_rank.p;
+        out->val = c->x_val.p;
+        out->mod = c->x_mod.p;
+    }
+    out->n = total;
+    out->n_live = w[1];
+    c->x_n = total;
+    c->x_valid = true;
+    return CRDT_OK;
+}
+
+int crdt_export_read(crdt_ctx* c, uint64_t first, uint64_t count, uint32_t* key_id, int64_t* lt,
+                     uint32_t* rank, uint32_t* val, int64_t* mod) {
+    if (!c || !c->x_valid || first > c->x_n || count > c->x_n - first) return CRDT_E_INVALID;
+    if (count == 0) return CRDT_OK;
+    HIPCHK(hipSetDevice(c->device));
+    if (key_id) HIPCHK(hipMemcpyAsync(key_id, c->x_key.p + first, count * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    if (lt) HIPCHK(hipMemcpyAsync(lt, c->x_lt.p + first, count * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    if (rank) HIPCHK(hipMemcpyAsync(rank, c->x_rank.p + first, count * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    if (val) HIPCHK(hipMemcpyAsync(val, c->x_val.p + first, count * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    if (mod) HIPCHK(hipMemcpyAsync(mod, c->x_mod.p + first, count * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return CRDT_OK;
+}
+
+int crdt_export_release(crdt_ctx* c) {
+    if (!c) return CRDT_E_INVALID;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    ex_drop(c);
+    c->x_counts.release();
+    c->x_offs.release();
     return CRDT_OK;
 }
 

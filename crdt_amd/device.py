@@ -89,6 +89,37 @@ class _Cols:
             raise ValueError("all columns of one call must live in the same memory (host or device)")
 
 
+class Export:
+    """A device-resident changeset (``crdt_export``): ``n`` records, ``n_live`` of them not
+    tombstones.  It belongs to the table that exported it and ends at that table's next
+    ``export_since``, ``export_release`` or ``close``; a view that has ended raises
+    ``CrdtNativeError(CRDT_E_INVALID)`` (the state is checked on the host, no memory is read)."""
+
+    def __init__(self, table: "DeviceTable", view, serial: int):
+        self._table = table
+        self._view = view
+        self._serial = serial
+        self.n = int(view.n)
+        self.n_live = int(view.n_live)
+        self.device = int(view.device)
+
+    def columns(self, first: int = 0, count: int | None = None):
+        """Host copies ``key, lt, rank, val, mod`` of records [first, first + count)."""
+        t = self._table
+        if self._serial != getattr(t, "_export_serial", 0) or not (t._ctx and t._ctx.value):
+            raise CrdtNativeError(_capi.CRDT_E_INVALID, "crdt_export_read (the view was replaced)")
+        count = self.n - first if count is None else int(count)
+        if first < 0 or count < 0:
+            raise CrdtNativeError(_capi.CRDT_E_INVALID, "crdt_export_read")
+        m = max(count, 0)
+        key, rank, val = np.empty(m, np.uint32), np.empty(m, np.uint32), np.empty(m, np.uint32)
+        lt, mod = np.empty(m, np.int64), np.empty(m, np.int64)
+        P = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+        t._check(t._lib.crdt_export_read(t._ctx, int(first), count, P(key), P(lt), P(rank), P(val), P(mod)),
+                 "crdt_export_read")
+        return key, lt, rank, val, mod
+
+
 class DeviceTable:
     """Rows ``{lt, rank, val, mod}`` indexed by key id, plus the canonical clock."""
 
@@ -183,6 +214,40 @@ class DeviceTable:
                     "crdt_modified_since")
         return out[:n.value]
 
+    # ------------------------------------- changeset export (crdt_export_since)
+    def export_since(self, n_rows: int, since: int) -> "Export":
+        """recordMap(modifiedSince) left on the device: the rows of [0, n_rows) with mod >= since as
+        one changeset, ascending by id.  The view ends at this table's next export_since / release."""
+        v = _capi.CrdtExport()
+        self._check(self._lib.crdt_export_since(self._ctx, int(n_rows), int(since), ctypes.byref(v)),
+                    "crdt_export_since")
+        self._export_serial = getattr(self, "_export_serial", 0) + 1
+        return Export(self, v, self._export_serial)
+
+    def count_since(self, n_rows: int, since: int) -> tuple[int, int]:
+        """(records, live records) export_since would select; the count pass alone."""
+        n, live = ctypes.c_uint64(), ctypes.c_uint64()
+        self._check(self._lib.crdt_count_since(self._ctx, int(n_rows), int(since), ctypes.byref(n),
+                                               ctypes.byref(live)), "crdt_count_since")
+        return n.value, live.value
+
+    def export_release(self):
+        self._check(self._lib.crdt_export_release(self._ctx), "crdt_export_release")
+
+    def merge_from(self, src: "DeviceTable", n_rows: int, since: int, wall: int, win_flags=True):
+        """``self.merge(src.recordMap(modifiedSince))`` between two tables of one device and one id
+        space: src's export is merged as ONE device changeset, nothing crossing to the host.
+        Returns (result dict, win flags) as ``merge`` does for a device batch."""
+        if src.device != self.device:
+            raise ValueError(f"merge_from: the source table is on device {src.device}, this one on {self.device}")
+        ex = src.export_since(n_rows, since)
+        offs = np.array([0, ex.n], np.uint64)
+        v = ex._view
+        b = CrdtBatch(v.key_id, v.lt, v.rank, v.val, None, offs.ctypes.data_as(ctypes.c_void_p), 1,
+                      _capi.CRDT_MEM_DEVICE)
+        import torch
+        return self._merge_batch(b, ex.n, torch.device("cuda", self.device), wall, win_flags)
+
     def clear_rows(self, first: int, count: int):
         self._check(self._lib.crdt_clear_rows(self._ctx, first, count), "crdt_clear_rows")
 
@@ -219,13 +284,18 @@ class DeviceTable:
         ``win_flags``: True -> a host uint8 array is returned; a torch uint8 CUDA tensor
         -> filled in place (device batches); False/None -> not produced."""
         b, c, offs = self._batch(key, lt, rank, val, offsets, millis)
-        n = int(offs[-1])
+        dev = c.keep[0].device if c.mem == _capi.CRDT_MEM_DEVICE else None
+        return self._merge_batch(b, int(offs[-1]), dev, wall, win_flags)
+
+    def _merge_batch(self, b, n: int, torch_device, wall: int, win_flags):
+        """crdt_merge of a built batch of n records; ``torch_device``: where a device batch's flags go
+        (None for a host batch)."""
         flags_arr = None
         fptr = None
         if win_flags is True:
-            if c.mem == _capi.CRDT_MEM_DEVICE:
+            if torch_device is not None:
                 import torch
-                flags_arr = torch.zeros(max(n, 1), dtype=torch.uint8, device=c.keep[0].device)
+                flags_arr = torch.zeros(max(n, 1), dtype=torch.uint8, device=torch_device)
                 torch_ready(flags_arr)                  # (its zero fill must not land after the merge)
                 fptr = ctypes.c_void_p(flags_arr.data_ptr())
             else:

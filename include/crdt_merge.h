@@ -163,6 +163,49 @@ int crdt_read_rows(crdt_ctx* ctx, const uint32_t* key_id, uint64_t n, int64_t* l
  * mod >= since_lt, ascending (= insertion order).  out_ids (HOST) holds n_rows. */
 int crdt_modified_since(crdt_ctx* ctx, uint64_t n_rows, int64_t since_lt, uint32_t* out_ids,
                         uint64_t* n_out);
+/* ---- changeset export: recordMap(modifiedSince) left on the device (crdt.dart:157-160) ----
+ * The rows of [0, n_rows) whose mod is not < since_lt (crdt_modified_since's predicate, on the raw
+ * signed 64-bit value), ascending by id, as the five columns of a changeset.  The export reads the
+ * table twice (a count pass, a scan of the tile counts, a write pass that skips tiles holding no
+ * selected row) and moves nothing to the host.
+ *
+ * Ownership: the columns belong to the ctx that exported them, in buffers of their own sized from the
+ * count pass (not the staging crdt_merge / crdt_put_rows reuse).  They stay valid until the next
+ * crdt_export_since, crdt_export_release or crdt_destroy on THAT ctx; calls on other ctxs, and merges
+ * or puts on the same ctx, leave them alone.  crdt_export_since is synchronous: the ctx's stream is
+ * drained before it returns, so another ctx's stream may read the columns at once.  n_rows == 0 and an
+ * empty selection give n = 0 (the pointers may then be NULL).
+ *
+ * Replica-to-replica sync.  For two ctxs on the SAME device whose host shares one key, node and value
+ * interning,
+ *     crdt_export v;  crdt_export_since(src, n_rows, since, &v);
+ *     uint64_t offs[2] = {0, v.n};
+ *     crdt_batch b = {v.key_id, v.lt, v.rank, v.val, NULL, offs, 1, CRDT_MEM_DEVICE};
+ *     crdt_merge(dst, &b, wall_millis, flags_or_NULL, &res);
+ * is dst.merge(src.recordMap(modifiedSince: since)) without a byte crossing to the host (an empty
+ * view is still one merge() call: the closing Hlc.send advances dst's canonical, crdt.dart:93).
+ * On a sharded ctx the export is rank-local and key_id holds slots, as crdt_modified_since's ids do. */
+typedef struct crdt_export {        /* a changeset: one Map<K, Record<V>> in insertion (id) order */
+    const uint32_t* key_id;
+    const int64_t* lt;
+    const uint32_t* rank;
+    const uint32_t* val;
+    const int64_t* mod;
+    uint64_t n;                /* records */
+    uint64_t n_live;           /* of them not tombstones (val != CRDT_NULL_VALUE) */
+    int32_t mem;               /* CRDT_MEM_DEVICE */
+    int32_t device;            /* the exporting ctx's device */
+} crdt_export;
+int crdt_export_since(crdt_ctx* ctx, uint64_t n_rows, int64_t since_lt, crdt_export* out);
+/* Records [first, first + count) of the ctx's current view copied to HOST arrays; any pointer may be
+ * NULL.  CRDT_E_INVALID without a view (none exported yet, or released) or past its end. */
+int crdt_export_read(crdt_ctx* ctx, uint64_t first, uint64_t count, uint32_t* key_id, int64_t* lt,
+                     uint32_t* rank, uint32_t* val, int64_t* mod);
+/* Ends the view and frees its buffers. */
+int crdt_export_release(crdt_ctx* ctx);
+/* The export's n and n_live alone: the count pass only, no column and nothing sized by the table is
+ * allocated (Crdt.length = n_live at since_lt = 0, crdt.dart:20). */
+int crdt_count_since(crdt_ctx* ctx, uint64_t n_rows, int64_t since_lt, uint64_t* n, uint64_t* n_live);
 /* purge() (map_crdt.dart:51-52) and rollback of interned-but-uncommitted ids. */
 int crdt_clear_rows(crdt_ctx* ctx, uint64_t first, uint64_t count);
 /* Re-rank stored node ids after the host inserts a new nodeId between existing
