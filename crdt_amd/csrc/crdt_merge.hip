@@ -1668,6 +1668,8 @@ __global__ __launch_bounds__(kExThreads) void k_ex_write(Table table, uint64_t n
     }
 }
 
+#include "table_merge.inc"
+
 __global__ __launch_bounds__(256) void k_fill_i64(long long* __restrict__ p, uint64_t n, long long v)
 {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1841,6 +1843,14 @@ struct crdt_ctx {
     DBuf<unsigned long long> x_words;  // [0] selected rows, [1] live ones (k_ex_count / k_ex_scan)
     bool x_valid = false;              // a view is out (host-side state: crdt_export_read checks it)
     uint64_t x_n = 0;
+    // crdt_merge_table (table_merge.inc), this ctx the destination: the tiles' selected rows, one selection
+    // bit per row, the clock pass's four words, and the composition's per-record win flags when the call
+    // falls back to it
+    DBuf<uint32_t> t_sel;
+    DBuf<unsigned long long> t_words, t_mask;
+    DBuf<uint8_t> t_wflags;
+    bool table_merge = true;           // CRDT_TABLE_MERGE=0: every crdt_merge_table takes the composition
+    bool last_table = false;           // the last merge on this ctx ran the fused table form
     DBuf<long long> d_word;
     DBuf<unsigned long long> d_ibase;
     // per-call plan (set by scan, used by later phases)
@@ -3509,6 +3519,7 @@ static void read_env_knobs(crdt_ctx* c) {
     if (const char* e = getenv("CRDT_XCD_MAP")) c->xcd_map = atoi(e) != 0;
     if (const char* e = getenv("CRDT_PACKED")) c->packed_resolve = atoi(e) != 0;
     if (const char* e = getenv("CRDT_FLAGS_SORTED")) c->flags_sorted = atoi(e) != 0;
+    if (const char* e = getenv("CRDT_TABLE_MERGE")) c->table_merge = atoi(e) != 0;
     if (const char* e = getenv("CRDT_COMBINE")) c->combine = std::min(std::max(atoi(e), 0), 2);
     if (const char* e = getenv("CRDT_ROUTE_L1")) c->route_l1 = std::min(std::max(atoi(e), 0), 3);
     if (const char* e = getenv("CRDT_RL1_SPLIT")) {   // 0: one piece, 1: two (the default), n: n pieces
@@ -3613,6 +3624,7 @@ void crdt_destroy(crdt_ctx* c) {
     c->s_millis.release(); c->s_mod.release(); c->s_flags.release(); c->s_out.release();
     c->x_key.release(); c->x_rank.release(); c->x_val.release(); c->x_lt.release(); c->x_mod.release();
     c->x_counts.release(); c->x_offs.release(); c->x_words.release();
+    c->t_sel.release(); c->t_words.release(); c->t_mask.release(); c->t_wflags.release();
     c->d_word.release();
     c->d_ibase.release();
     c->p1_rec.release(); c->p1_kj.release(); c->p2_rec.release(); c->p2_kj.release();
@@ -4022,6 +4034,7 @@ int crdt_merge(crdt_ctx* c, const crdt_batch* batch, int64_t wall, uint8_t* win_
     }
     HIPCHK(hipSetDevice(c->device));
     if (c->env_dynamic) read_env_knobs(c);
+    c->last_table = false;
     // rows >= hw_read are read as the fill by this merge; afterwards hw moves to hw_next (the
     // capacity unless finish_apply learned the batch's key bound) on every return path
     c->hw_read = (c->form_off & kFormNoHw) ? c->cap : c->hw;
@@ -4088,6 +4101,161 @@ int crdt_merge(crdt_ctx* c, const crdt_batch* batch, int64_t wall, uint8_t* win_
     return st;
 }
 
+// ---- crdt_merge_table: dst.merge(src.recordMap(modifiedSince)) over two aligned tables (table_merge.inc)
+// The composition itself: export src's selection, merge it into dst as one device changeset, carry the
+// per-record win flags to their row ids.  Exact by construction; the fused form falls back to it whenever
+// a recv() may raise or a selected id lies outside dst.  src's own export view survives it: its columns
+// are set aside while the temporary view exists.
+static int table_merge_composed(crdt_ctx* dst, crdt_ctx* src, uint64_t n_rows, int64_t since, int64_t wall,
+                                uint8_t* row_flags, int32_t flags_mem, crdt_result* out) {
+    struct Saved {
+        crdt_ctx* s;
+        DBuf<uint32_t> key, rank, val;
+        DBuf<int64_t> lt, mod;
+        bool valid;
+        uint64_t n;
+        explicit Saved(crdt_ctx* c) : s(c), key(c->x_key), rank(c->x_rank), val(c->x_val), lt(c->x_lt),
+                                      mod(c->x_mod), valid(c->x_valid), n(c->x_n) {
+            c->x_key = {}; c->x_rank = {}; c->x_val = {}; c->x_lt = {}; c->x_mod = {};
+        }
+        ~Saved() {
+            ex_drop(s);                                     // the temporary view's columns
+            s->x_key = key; s->x_rank = rank; s->x_val = val; s->x_lt = lt; s->x_mod = mod;
+            s->x_valid = valid;
+            s->x_n = n;
+        }
+    } saved(src);
+    crdt_export v;
+    int st = crdt_export_since(src, n_rows, since, &v);
+    if (st) return st;
+    uint8_t* wf = nullptr;
+    if (row_flags) {
+        HIPALLOC(dst->t_wflags.ensure(v.n ? v.n : 1));
+        wf = dst->t_wflags.p;
+    }
+    const uint64_t offs[2] = {0, v.n};
+    const crdt_batch b = {v.key_id, v.lt, v.rank, v.val, nullptr, offs, 1, CRDT_MEM_DEVICE};
+    st = crdt_merge(dst, &b, wall, wf, out);
+    if (row_flags && n_rows && (st >= 0 || st == CRDT_E_KEY_RANGE)) {
+        uint8_t* rf = row_flags;
+        if (flags_mem == CRDT_MEM_HOST) {
+            HIPALLOC(dst->s_flags.ensure(n_rows));
+            rf = dst->s_flags.p;
+        }
+        HIPCHK(hipMemsetAsync(rf, 0, n_rows, dst->stream));
+        if (v.n) {
+            k_tm_flags_scatter<<<std::min<uint32_t>(grid_for(v.n, 256), 8192), 256, 0, dst->stream>>>(
+                v.key_id, wf, v.n, n_rows, rf);
+            HIPCHK(hipGetLastError());
+        }
+        if (flags_mem == CRDT_MEM_HOST)
+            HIPCHK(hipMemcpyAsync(row_flags, rf, n_rows, hipMemcpyDeviceToHost, dst->stream));
+        HIPCHK(hipStreamSynchronize(dst->stream));
+    }
+    return st;
+}
+
+int crdt_merge_table(crdt_ctx* dst, crdt_ctx* src, uint64_t n_rows, int64_t since_lt, int64_t wall,
+                     uint8_t* row_flags, int32_t flags_mem, crdt_result* out) {
+    if (!dst || !src || !out || n_rows > src->cap || dst->device != src->device || dst->has_comm ||
+        src->has_comm)
+        return CRDT_E_INVALID;
+    if (row_flags && flags_mem != CRDT_MEM_HOST && flags_mem != CRDT_MEM_DEVICE) return CRDT_E_INVALID;
+    HIPCHK(hipSetDevice(dst->device));
+    if (dst->env_dynamic) read_env_knobs(dst);
+    // the composition: switched to, a self-merge (the passes would read rows they write), or a ctx whose
+    // merges are pinned to the sorted path (its order-free form reports no per-record counts)
+    if (!dst->table_merge || src == dst || dst->merge_path == CRDT_PATH_SORTED)
+        return table_merge_composed(dst, src, n_rows, since_lt, wall, row_flags, flags_mem, out);
+    HIPCHK(hipStreamSynchronize(src->stream));        // src's rows are final before dst's stream reads them
+    const uint64_t rows = ex_rows(src, n_rows, since_lt);
+    const unsigned nb = grid_for(rows, kTmTile);
+    HIPALLOC(dst->t_words.ensure(4));
+    HIPALLOC(dst->t_sel.ensure(nb ? nb : 1));
+    HIPALLOC(dst->t_mask.ensure(nb ? (size_t)nb * kTmMaskWords : 1));
+    uint8_t* rf = row_flags;
+    if (row_flags && flags_mem == CRDT_MEM_HOST) {
+        HIPALLOC(dst->s_flags.ensure(n_rows ? n_rows : 1));
+        rf = dst->s_flags.p;
+    }
+    if (dst->timing) HIPCHK(ensure_events(dst, events_for(1)));
+    dst->windows.clear();
+    dst->apply_total = 0;
+    dst->sent_bytes = 0;
+    ev_record(dst, kEvStart);
+    // pass 1: the clock words of src's selection
+    const int64_t c0 = dst->canonical;
+    HIPCHK(hipMemsetAsync(dst->t_words.p, 0, 4 * sizeof(unsigned long long), dst->stream));
+    if (rows) {
+        k_tm_clock<<<std::min(nb, kTmClockGrid), kTmThreads, 0, dst->stream>>>(
+            src->table, rows, since_lt, nb, c0, wall, dst->local_rank, dst->t_sel.p, dst->t_mask.p, dst->t_words.p);
+        HIPCHK(hipGetLastError());
+    }
+    ev_record(dst, kEvScan);
+    unsigned long long w[4] = {0, 0, 0, 0};
+    HIPCHK(hipMemcpyAsync(w, dst->t_words.p, sizeof(w), hipMemcpyDeviceToHost, dst->stream));
+    HIPCHK(hipStreamSynchronize(dst->stream));
+    const bool has = w[3] != 0;
+    // a selected row may raise in recv(), or lies outside dst: nothing is written yet, the composition
+    // gives the exact stop point, exception details and error
+    if (w[2] || (has && w[1] > dst->cap))
+        return table_merge_composed(dst, src, n_rows, since_lt, wall, row_flags, flags_mem, out);
+    // the recv loop leaves R = max(C_0, M) (crdt.dart:82); the rows are stored with mod = R, then
+    // Hlc.send(R) (hlc.dart:51-74, crdt.dart:93) fixes the canonical or raises after the store
+    const int64_t R = has ? imax(c0, (int64_t)(w[0] ^ (1ull << 63))) : c0;
+    crdt_result res;
+    memset(&res, 0, sizeof(res));
+    res.exc_index = UINT64_MAX;
+    res.n_stored = 1;
+    const int64_t rm = R >> kShift, rc = R & kMaxCounter;
+    const int64_t mn = imax(rm, wall);
+    const int64_t cn = (rm == mn) ? rc + 1 : 0;
+    if (wsub(mn, wall) > kMaxDrift) {
+        res.status = CRDT_CLOCK_DRIFT;
+        res.drift_ms = wsub(mn, wall);
+        res.canonical_lt = R;
+    } else if (cn > kMaxCounter) {
+        res.status = CRDT_OVERFLOW;
+        res.counter = cn;
+        res.canonical_lt = R;
+    } else {
+        res.canonical_lt = (int64_t)(((uint64_t)mn << kShift) + (uint64_t)cn);
+    }
+    ev_record(dst, kEvClock);
+    // pass 2: the winners into dst
+    int st;
+    if ((st = reset_misc(dst))) return st;
+    // the apply pass writes the flag of every row it covers, [0, rows); the host zeroes the rest
+    const uint64_t covered = has ? rows : 0;
+    if (rf && n_rows > covered) HIPCHK(hipMemsetAsync(rf + covered, 0, n_rows - covered, dst->stream));
+    ev_record(dst, kEvApply);
+    if (has) {
+        ev_record(dst, ev_window(0, false));
+        k_tm_apply<<<nb, kTmThreads, 0, dst->stream>>>(src->table, dst->table, rows, dst->cap, dst->t_sel.p,
+                                                       dst->t_mask.p, R, dst->d_misc, rf);
+        HIPCHK(hipGetLastError());
+        ev_record(dst, ev_window(0, true));
+        if (dst->timing) dst->windows.push_back(1u);
+        dst->apply_total = 1;
+    }
+    ev_record(dst, kEvEnd);
+    HIPCHK(hipMemcpyAsync(dst->h_misc, dst->d_misc, sizeof(Misc), hipMemcpyDeviceToHost, dst->stream));
+    if (row_flags && flags_mem == CRDT_MEM_HOST && n_rows)
+        HIPCHK(hipMemcpyAsync(row_flags, rf, n_rows, hipMemcpyDeviceToHost, dst->stream));
+    HIPCHK(hipStreamSynchronize(dst->stream));
+    for (int s = 0; s < kCounterSlots; ++s) {
+        res.n_present += dst->h_misc->present[s];
+        res.n_won += dst->h_misc->won[s];
+    }
+    if (has) raise_hw(dst, w[1]);                     // every row written is a selected one
+    dst->canonical = res.canonical_lt;
+    dst->last_table = true;
+    dst->last_sorted = false;
+    collect_timing(dst);
+    *out = res;
+    return res.status;
+}
+
 int crdt_set_rank_bound(crdt_ctx* c, uint32_t bound) {
     if (!c) return CRDT_E_INVALID;
     c->rank_bound = bound;
@@ -4115,6 +4283,7 @@ int crdt_last_path(const crdt_ctx* c, int* path) {
 int crdt_last_plan(const crdt_ctx* c, uint32_t* flags) {
     if (!c || !flags) return CRDT_E_INVALID;
     uint32_t f = 0;
+    if (c->last_table) { *flags = CRDT_PLAN_TABLE; return CRDT_OK; }
     if (c->last_sorted) {
         f |= CRDT_PLAN_SORTED;
         if (c->last_packed) f |= CRDT_PLAN_PACKED;

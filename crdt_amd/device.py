@@ -248,6 +248,41 @@ class DeviceTable:
         import torch
         return self._merge_batch(b, ex.n, torch.device("cuda", self.device), wall, win_flags)
 
+    def merge_table(self, src: "DeviceTable", n_rows: int, since: int, wall: int, row_flags=False):
+        """``self.merge(src.recordMap(modifiedSince))`` as ``merge_from`` computes it, in two streaming
+        passes over the two tables and without an export (``crdt_merge_table``).  Returns (result dict,
+        row flags or None): the flags are indexed by ROW id, one byte for each of ``n_rows`` rows, 1 where
+        this table's row was stored.  ``row_flags``: True -> a torch uint8 tensor on the table's device;
+        a torch uint8 CUDA tensor -> filled in place; a numpy uint8 array -> host memory, filled in place;
+        False/None -> not produced."""
+        if src.device != self.device:
+            raise ValueError(f"merge_table: the source table is on device {src.device}, this one on {self.device}")
+        n_rows = int(n_rows)
+        flags_arr, fptr, mem = None, None, _capi.CRDT_MEM_DEVICE
+        if row_flags is True:
+            import torch
+            flags_arr = torch.zeros(max(n_rows, 1), dtype=torch.uint8, device=torch.device("cuda", self.device))
+            torch_ready(flags_arr)                      # (its zero fill must not land after the merge)
+            fptr = ctypes.c_void_p(flags_arr.data_ptr())
+        elif row_flags is not None and row_flags is not False:
+            flags_arr = row_flags
+            if _is_torch(row_flags):
+                if not row_flags.is_cuda or row_flags.numel() < n_rows:
+                    raise ValueError("row_flags must be a CUDA uint8 tensor of one entry per row")
+                fptr = self._dptr(row_flags, "u1", "row_flags")
+            else:
+                if row_flags.dtype != np.uint8 or not row_flags.flags.c_contiguous or len(row_flags) < n_rows:
+                    raise ValueError("row_flags must be a contiguous uint8 array of one entry per row")
+                fptr = row_flags.ctypes.data_as(ctypes.c_void_p)
+                mem = _capi.CRDT_MEM_HOST
+        res = CrdtResult()
+        st = self._lib.crdt_merge_table(self._ctx, src._ctx, n_rows, int(since), int(wall), fptr, mem,
+                                        ctypes.byref(res))
+        self._check(st, "crdt_merge_table")
+        if row_flags is True:
+            flags_arr = flags_arr[:n_rows]
+        return res.as_dict(), flags_arr
+
     def clear_rows(self, first: int, count: int):
         self._check(self._lib.crdt_clear_rows(self._ctx, first, count), "crdt_clear_rows")
 
@@ -402,7 +437,7 @@ class DeviceTable:
                   "high_water": 64, "anchored": 128, "wire_packed": 256, "own_in_place": 512,
                   "flagged": 1024, "ordered": 2048,
                   "combined": 4096, "route_l1": 8192, "route_tuned": 16384, "rl1_head": 262144,
-                  "compact": 524288, "hot_direct": 1048576}
+                  "compact": 524288, "hot_direct": 1048576, "table": 2097152}
 
     def last_plan(self) -> dict:
         """crdt_last_plan: how the last merge ran ({'sorted': bool, 'packed': ..., ...})."""

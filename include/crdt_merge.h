@@ -232,6 +232,34 @@ int crdt_refresh_canonical(crdt_ctx* ctx, uint64_t n_rows, int64_t* out_lt);
 int crdt_merge(crdt_ctx* ctx, const crdt_batch* batch, int64_t wall_millis, uint8_t* win_flags,
                crdt_result* out);
 
+/* dst.merge(src.recordMap(modifiedSince)) for two ctxs on the SAME device sharing one key / node / value
+ * interning, without an export: ONE merge() call (crdt.dart:77-94) whose changeset is the rows of
+ * src [0, n_rows) with !(mod < since_lt), ascending by id.  For every input it leaves exactly what
+ *     crdt_export_since(src, n_rows, since_lt, &v);
+ *     crdt_merge(dst, {v.key_id, v.lt, v.rank, v.val, NULL, {0, v.n}, 1, CRDT_MEM_DEVICE}, wall_millis, flags, out)
+ * leaves — dst's rows and canonical, every field of crdt_result, the return status (an empty selection
+ * is still one merge() call; exc_index counts among the selected rows; CRDT_E_KEY_RANGE, with nothing
+ * stored, when a selected id is >= dst's capacity) — and src's rows, canonical and export view untouched.
+ * Key k is row k of both tables, so the merge is two streaming passes and allocates nothing that grows
+ * with the selection (its scratch: a count per tile and one bit per row): a clock pass over src (each
+ * tile's selected rows, a selection bit per row, the selection's max lt and id, whether any selected row
+ * may raise in recv()), a read-back of four words, and an apply pass that skips the tiles holding no
+ * selected row, reads the selected rows of both tables and stores the winners with mod = the canonical
+ * after the recv loop.
+ * Whenever a selected row may raise (lt above dst's canonical with dst's node id, or over 60000 ms ahead
+ * of wall_millis), a selected id lies outside dst, src == dst, dst is pinned to CRDT_PATH_SORTED, or the
+ * environment says CRDT_TABLE_MERGE=0 (read at crdt_create of dst), the call runs the composition above
+ * itself: nothing has been written by then.
+ * row_flags (optional, memory of kind flags_mem): [n_rows] bytes indexed by ROW id, every entry written:
+ * 1 where dst's row was stored, else 0 (the composition's win flags at their key ids: the watch() events).
+ * CRDT_E_INVALID, nothing touched: a null ctx or out, n_rows > src's capacity, different devices, a ctx
+ * joined to a communicator.  Neither ctx may be in another call; the work runs on dst's stream after
+ * src's is drained, and the call is synchronous.  Afterwards crdt_last_path(dst) is CRDT_PATH_GATHER and
+ * crdt_last_plan(dst) CRDT_PLAN_TABLE alone (after a fallback: what the composition's crdt_merge reports);
+ * crdt_timing gets scan_ms (the clock pass), apply_ms (the apply pass) and total_ms. */
+int crdt_merge_table(crdt_ctx* dst, crdt_ctx* src, uint64_t n_rows, int64_t since_lt, int64_t wall_millis,
+                     uint8_t* row_flags, int32_t flags_mem, crdt_result* out);
+
 /* ---- key-sharded multi-GPU (north star config 4) -------------
  * n_ranks ctxs — one per GPU, normally one process per GPU — form ONE replica whose
  * keys are sharded: rank d owns key k iff k % n_ranks == d and stores it at slot
@@ -380,9 +408,11 @@ enum crdt_plan_flags {
                                     (lt >> 16 - min, lt & 0xFFFF) in as many bits as the batch needs, so a record's
                                     whole 20-bit level-1 slot rides in its 64-bit key: 12-B partition records
                                     (sorted_path.inc, PackFrame::cb) */
-    CRDT_PLAN_HOT_DIRECT = 1048576 /* the compact order-free form of a two-level table: level 1 wrote the records of
+    CRDT_PLAN_HOT_DIRECT = 1048576, /* the compact order-free form of a two-level table: level 1 wrote the records of
                                     the first CRDT_HOT_BUCKETS final buckets (keys < H * 4096) straight into their
                                     final bucket; they skipped level 2 (sorted_path.inc, HotL1) */
+    CRDT_PLAN_TABLE = 2097152     /* the last merge on this ctx was a crdt_merge_table that ran the fused table
+                                    form (table_merge.inc); set alone */
 };
 int crdt_last_plan(const crdt_ctx* ctx, uint32_t* flags);
 
