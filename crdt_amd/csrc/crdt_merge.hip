@@ -1386,6 +1386,7 @@ __global__ __launch_bounds__(256) void k_put_stamped(
 {
     unsigned long long kend = 0;
     bool bad = false;
+    if (misc->err) return;                        // k_key_check saw an id >= cap: the call stores nothing
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
         const uint32_t k = key[i];
         if (k >= cap) { bad = true; continue; }
@@ -1693,10 +1694,12 @@ __global__ __launch_bounds__(256) void k_remap(Table table, uint64_t n,
 
 // ============================================================ host-side context
 // CRDT_POISON_ALLOC=1 (debug): every scratch allocation is filled with 0x5A bytes, so a kernel that
-// reads scratch it never wrote gives the same wrong answer on every run instead of stale data's
+// reads scratch it never wrote gives the same wrong answer on every run instead of stale data's.
+// Read at every allocation (DBuf::ensure allocating or growing; never in a steady-state merge), so a
+// test can switch it on for the contexts it creates.
 static bool poison_alloc() {
-    static const int v = [] { const char* e = getenv("CRDT_POISON_ALLOC"); return e && atoi(e) ? 1 : 0; }();
-    return v != 0;
+    const char* e = getenv("CRDT_POISON_ALLOC");
+    return e && atoi(e);
 }
 template <typename T>
 struct DBuf {
@@ -3791,6 +3794,8 @@ int crdt_put_stamped(crdt_ctx* c, const uint32_t* key_id, const uint32_t* val, u
     if ((st = stage(c, c->s_key, key_id, n, mem, &dk))) return st;
     if ((st = stage(c, c->s_val, val, n, mem, &dv))) return st;
     if ((st = reset_misc(c))) return st;
+    // every id against the capacity first: a call with a bad id stores no row (as the restatement's putAll)
+    k_key_check<<<std::min<uint32_t>(grid_for(n, 256 * 16), 8192), 256, 0, c->stream>>>(dk, n, c->cap, c->d_misc);
     k_put_stamped<<<std::min<uint32_t>(grid_for(n, 256), kPutGrid), 256, 0, c->stream>>>(
         dk, dv, n, stamp, c->local_rank, c->table, c->cap, c->d_misc);
     HIPCHK(hipGetLastError());

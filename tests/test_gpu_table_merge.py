@@ -19,7 +19,7 @@ I64_MIN = tc.I64_MIN
 U64_MAX = (1 << 64) - 1
 MW = tc.MERGE_WALL
 RESULT_FIELDS = gx.RESULT_FIELDS
-STRIDES = [(24, 24), (24, 32), (32, 24)]
+STRIDES = [(24, 24), (24, 32), (32, 24), (32, 32)]
 
 
 def load(rows: dict, capacity: int, row_bytes: int = 24, local_rank: int = 0, canonical: int = 0):
