@@ -1854,6 +1854,7 @@ struct crdt_ctx {
     DBuf<uint8_t> t_wflags;
     bool table_merge = true;           // CRDT_TABLE_MERGE=0: every crdt_merge_table takes the composition
     bool last_table = false;           // the last merge on this ctx ran the fused table form
+    bool last_sync = false;            // ... as one side of a fused crdt_sync_tables
     DBuf<long long> d_word;
     DBuf<unsigned long long> d_ibase;
     // per-call plan (set by scan, used by later phases)
@@ -4040,6 +4041,7 @@ int crdt_merge(crdt_ctx* c, const crdt_batch* batch, int64_t wall, uint8_t* win_
     HIPCHK(hipSetDevice(c->device));
     if (c->env_dynamic) read_env_knobs(c);
     c->last_table = false;
+    c->last_sync = false;
     // rows >= hw_read are read as the fill by this merge; afterwards hw moves to hw_next (the
     // capacity unless finish_apply learned the batch's key bound) on every return path
     c->hw_read = (c->form_off & kFormNoHw) ? c->cap : c->hw;
@@ -4255,10 +4257,158 @@ int crdt_merge_table(crdt_ctx* dst, crdt_ctx* src, uint64_t n_rows, int64_t sinc
     if (has) raise_hw(dst, w[1]);                     // every row written is a selected one
     dst->canonical = res.canonical_lt;
     dst->last_table = true;
+    dst->last_sync = false;
     dst->last_sorted = false;
     collect_timing(dst);
     *out = res;
     return res.status;
+}
+
+// ---- crdt_sync_tables: a.merge(b.recordMap(since_b)), then b.merge(a.recordMap(since_a)) (table_merge.inc)
+// The composition itself: the two crdt_merge_table calls of the contract, the second only after a clean
+// first (an exception in a.merge ends the exchange).  Exact by construction; the fused form falls back to
+// it, with nothing written yet, whenever either direction may raise.
+static int sync_tables_composed(crdt_ctx* a, crdt_ctx* b, uint64_t n_rows, int64_t since_a, int64_t since_b,
+                                int64_t wall, uint8_t* flags_a, uint8_t* flags_b, int32_t flags_mem,
+                                crdt_result* out_a, crdt_result* out_b) {
+    const int s1 = crdt_merge_table(a, b, n_rows, since_b, wall, flags_a, flags_mem, out_a);
+    if (s1 == 0) return crdt_merge_table(b, a, n_rows, since_a, wall, flags_b, flags_mem, out_b);
+    memset(out_b, 0, sizeof(*out_b));
+    out_b->exc_index = UINT64_MAX;
+    out_b->canonical_lt = b->canonical;
+    if (flags_b && n_rows) {
+        if (flags_mem == CRDT_MEM_HOST) {
+            memset(flags_b, 0, n_rows);
+        } else {
+            HIPCHK(hipMemsetAsync(flags_b, 0, n_rows, a->stream));
+            HIPCHK(hipStreamSynchronize(a->stream));
+        }
+    }
+    return s1;
+}
+
+// Hlc.send(R) at the wall (hlc.dart:51-74) into res: the canonical it leaves, or the exception it raises
+// after the store (crdt.dart:93), as crdt_merge_table evaluates it.
+static void sync_send(int64_t R, int64_t wall, crdt_result* res) {
+    const int64_t rm = R >> kShift, rc = R & kMaxCounter;
+    const int64_t mn = imax(rm, wall);
+    const int64_t cn = (rm == mn) ? rc + 1 : 0;
+    if (wsub(mn, wall) > kMaxDrift) {
+        res->status = CRDT_CLOCK_DRIFT;
+        res->drift_ms = wsub(mn, wall);
+        res->canonical_lt = R;
+    } else if (cn > kMaxCounter) {
+        res->status = CRDT_OVERFLOW;
+        res->counter = cn;
+        res->canonical_lt = R;
+    } else {
+        res->canonical_lt = (int64_t)(((uint64_t)mn << kShift) + (uint64_t)cn);
+    }
+}
+
+int crdt_sync_tables(crdt_ctx* a, crdt_ctx* b, uint64_t n_rows, int64_t since_a, int64_t since_b, int64_t wall,
+                     uint8_t* flags_a, uint8_t* flags_b, int32_t flags_mem, crdt_result* out_a,
+                     crdt_result* out_b) {
+    if (!a || !b || !out_a || !out_b || n_rows > a->cap || n_rows > b->cap || a->device != b->device ||
+        a->has_comm || b->has_comm)
+        return CRDT_E_INVALID;
+    if ((flags_a || flags_b) && flags_mem != CRDT_MEM_HOST && flags_mem != CRDT_MEM_DEVICE) return CRDT_E_INVALID;
+    HIPCHK(hipSetDevice(a->device));
+    if (a->env_dynamic) read_env_knobs(a);
+    if (b->env_dynamic) read_env_knobs(b);
+    // the composition: switched to, a self-sync, or a ctx pinned to the sorted path (as crdt_merge_table)
+    if (!a->table_merge || !b->table_merge || a == b || a->merge_path == CRDT_PATH_SORTED ||
+        b->merge_path == CRDT_PATH_SORTED)
+        return sync_tables_composed(a, b, n_rows, since_a, since_b, wall, flags_a, flags_b, flags_mem, out_a, out_b);
+    HIPCHK(hipStreamSynchronize(b->stream));          // b's rows are final before a's stream reads and writes them
+    const uint64_t rows = std::max(ex_rows(a, n_rows, since_a), ex_rows(b, n_rows, since_b));
+    const unsigned nb = grid_for(rows, kTmTile);
+    HIPALLOC(a->t_words.ensure(kSyWords));
+    HIPALLOC(a->t_sel.ensure(nb ? nb : 1));
+    HIPALLOC(a->t_mask.ensure(nb ? (size_t)nb * kTmMaskWords * 2 : 1));
+    uint8_t *rfa = flags_a, *rfb = flags_b;
+    if (flags_mem == CRDT_MEM_HOST) {
+        if (flags_a) { HIPALLOC(a->s_flags.ensure(n_rows ? n_rows : 1)); rfa = a->s_flags.p; }
+        if (flags_b) { HIPALLOC(b->s_flags.ensure(n_rows ? n_rows : 1)); rfb = b->s_flags.p; }
+    }
+    if (a->timing) HIPCHK(ensure_events(a, events_for(1)));
+    a->windows.clear();
+    a->apply_total = 0;
+    a->sent_bytes = 0;
+    ev_record(a, kEvStart);
+    // pass 1: the clock words of both directions
+    const int64_t ca = a->canonical, cb = b->canonical;
+    HIPCHK(hipMemsetAsync(a->t_words.p, 0, kSyWords * sizeof(unsigned long long), a->stream));
+    if (rows) {
+        k_sy_clock<<<std::min(nb, kSyClockGrid), kTmThreads, 0, a->stream>>>(
+            a->table, b->table, rows, since_a, since_b, nb, ca, cb, wall, a->local_rank, b->local_rank, a->t_sel.p,
+            a->t_mask.p, a->t_words.p);
+        HIPCHK(hipGetLastError());
+    }
+    ev_record(a, kEvScan);
+    unsigned long long w[kSyWords] = {};
+    HIPCHK(hipMemcpyAsync(w, a->t_words.p, sizeof(w), hipMemcpyDeviceToHost, a->stream));
+    HIPCHK(hipStreamSynchronize(a->stream));
+    const bool has1 = w[3] != 0, has2 = w[7] != 0;
+    // the recv loops leave R_a = max(C_a, M_b) and R_b = max(C_b, M_a') (crdt.dart:82)
+    const int64_t Ra = has1 ? imax(ca, (int64_t)(w[0] ^ (1ull << 63))) : ca;
+    const int64_t Rb = has2 ? imax(cb, (int64_t)(w[4] ^ (1ull << 63))) : cb;
+    crdt_result ra, rb;
+    memset(&ra, 0, sizeof(ra));
+    memset(&rb, 0, sizeof(rb));
+    ra.exc_index = rb.exc_index = UINT64_MAX;
+    ra.n_stored = rb.n_stored = 1;
+    sync_send(Ra, wall, &ra);
+    sync_send(Rb, wall, &rb);
+    // a row may raise in either recv(), step 1's send() raises (the exchange ends there), or step 1's
+    // winners, stamped mod = R_a, would not be selected by since_a (direction 2's words assumed they are):
+    // nothing is written yet, the composition gives the exact stop points and exception details
+    if (w[2] || w[6] || ra.status != CRDT_OK || Ra < since_a)
+        return sync_tables_composed(a, b, n_rows, since_a, since_b, wall, flags_a, flags_b, flags_mem, out_a, out_b);
+    ev_record(a, kEvClock);
+    // pass 2: the winners into both tables (step 2's send() raising after its store stays in place)
+    int st;
+    if ((st = reset_misc(a))) return st;
+    const bool has = has1 || has2;
+    const uint64_t covered = has ? rows : 0;          // the apply pass writes the flags of [0, rows)
+    if (n_rows > covered) {
+        if (rfa) HIPCHK(hipMemsetAsync(rfa + covered, 0, n_rows - covered, a->stream));
+        if (rfb) HIPCHK(hipMemsetAsync(rfb + covered, 0, n_rows - covered, a->stream));
+    }
+    ev_record(a, kEvApply);
+    if (has) {
+        ev_record(a, ev_window(0, false));
+        k_sy_apply<<<nb, kTmThreads, 0, a->stream>>>(a->table, b->table, rows, a->t_sel.p, a->t_mask.p, Ra, Rb,
+                                                     a->d_misc, rfa, rfb);
+        HIPCHK(hipGetLastError());
+        ev_record(a, ev_window(0, true));
+        if (a->timing) a->windows.push_back(1u);
+        a->apply_total = 1;
+    }
+    ev_record(a, kEvEnd);
+    HIPCHK(hipMemcpyAsync(a->h_misc, a->d_misc, sizeof(Misc), hipMemcpyDeviceToHost, a->stream));
+    if (flags_mem == CRDT_MEM_HOST && n_rows) {
+        if (flags_a) HIPCHK(hipMemcpyAsync(flags_a, rfa, n_rows, hipMemcpyDeviceToHost, a->stream));
+        if (flags_b) HIPCHK(hipMemcpyAsync(flags_b, rfb, n_rows, hipMemcpyDeviceToHost, a->stream));
+    }
+    HIPCHK(hipStreamSynchronize(a->stream));
+    for (int s = 0; s < kCounterSlots / 2; ++s) {
+        ra.n_present += a->h_misc->present[s];
+        ra.n_won += a->h_misc->won[s];
+        rb.n_present += a->h_misc->present[kCounterSlots / 2 + s];
+        rb.n_won += a->h_misc->won[kCounterSlots / 2 + s];
+    }
+    if (has1) raise_hw(a, w[1]);                      // every row written is a selected one, on either side
+    if (has2) raise_hw(b, w[5]);
+    a->canonical = ra.canonical_lt;
+    b->canonical = rb.canonical_lt;
+    a->last_table = b->last_table = true;
+    a->last_sync = b->last_sync = true;
+    a->last_sorted = b->last_sorted = false;
+    collect_timing(a);
+    *out_a = ra;
+    *out_b = rb;
+    return rb.status;
 }
 
 int crdt_set_rank_bound(crdt_ctx* c, uint32_t bound) {
@@ -4288,7 +4438,7 @@ int crdt_last_path(const crdt_ctx* c, int* path) {
 int crdt_last_plan(const crdt_ctx* c, uint32_t* flags) {
     if (!c || !flags) return CRDT_E_INVALID;
     uint32_t f = 0;
-    if (c->last_table) { *flags = CRDT_PLAN_TABLE; return CRDT_OK; }
+    if (c->last_table) { *flags = CRDT_PLAN_TABLE | (c->last_sync ? CRDT_PLAN_SYNC : 0u); return CRDT_OK; }
     if (c->last_sorted) {
         f |= CRDT_PLAN_SORTED;
         if (c->last_packed) f |= CRDT_PLAN_PACKED;

@@ -248,16 +248,8 @@ class DeviceTable:
         import torch
         return self._merge_batch(b, ex.n, torch.device("cuda", self.device), wall, win_flags)
 
-    def merge_table(self, src: "DeviceTable", n_rows: int, since: int, wall: int, row_flags=False):
-        """``self.merge(src.recordMap(modifiedSince))`` as ``merge_from`` computes it, in two streaming
-        passes over the two tables and without an export (``crdt_merge_table``).  Returns (result dict,
-        row flags or None): the flags are indexed by ROW id, one byte for each of ``n_rows`` rows, 1 where
-        this table's row was stored.  ``row_flags``: True -> a torch uint8 tensor on the table's device;
-        a torch uint8 CUDA tensor -> filled in place; a numpy uint8 array -> host memory, filled in place;
-        False/None -> not produced."""
-        if src.device != self.device:
-            raise ValueError(f"merge_table: the source table is on device {src.device}, this one on {self.device}")
-        n_rows = int(n_rows)
+    def _row_flags_arg(self, row_flags, n_rows: int):
+        """(array to return, pointer, memory kind) of a ``row_flags`` argument of merge_table / sync_tables."""
         flags_arr, fptr, mem = None, None, _capi.CRDT_MEM_DEVICE
         if row_flags is True:
             import torch
@@ -275,6 +267,19 @@ class DeviceTable:
                     raise ValueError("row_flags must be a contiguous uint8 array of one entry per row")
                 fptr = row_flags.ctypes.data_as(ctypes.c_void_p)
                 mem = _capi.CRDT_MEM_HOST
+        return flags_arr, fptr, mem
+
+    def merge_table(self, src: "DeviceTable", n_rows: int, since: int, wall: int, row_flags=False):
+        """``self.merge(src.recordMap(modifiedSince))`` as ``merge_from`` computes it, in two streaming
+        passes over the two tables and without an export (``crdt_merge_table``).  Returns (result dict,
+        row flags or None): the flags are indexed by ROW id, one byte for each of ``n_rows`` rows, 1 where
+        this table's row was stored.  ``row_flags``: True -> a torch uint8 tensor on the table's device;
+        a torch uint8 CUDA tensor -> filled in place; a numpy uint8 array -> host memory, filled in place;
+        False/None -> not produced."""
+        if src.device != self.device:
+            raise ValueError(f"merge_table: the source table is on device {src.device}, this one on {self.device}")
+        n_rows = int(n_rows)
+        flags_arr, fptr, mem = self._row_flags_arg(row_flags, n_rows)
         res = CrdtResult()
         st = self._lib.crdt_merge_table(self._ctx, src._ctx, n_rows, int(since), int(wall), fptr, mem,
                                         ctypes.byref(res))
@@ -282,6 +287,32 @@ class DeviceTable:
         if row_flags is True:
             flags_arr = flags_arr[:n_rows]
         return res.as_dict(), flags_arr
+
+    def sync_tables(self, other: "DeviceTable", n_rows: int, since_self: int, since_other: int, wall: int,
+                    row_flags=False):
+        """The two-replica exchange ``self.merge(other.recordMap(modifiedSince: since_other))`` then
+        ``other.merge(self.recordMap(modifiedSince: since_self))``, both decided on one read of the two
+        tables (``crdt_sync_tables``); exactly what the two ``merge_table`` calls leave, the second skipped
+        when the first raises.  Returns ((result of self, its row flags), (result of other, its row flags)).
+        ``row_flags``: as ``merge_table``'s, or a pair (for self, for other) of arrays of one memory kind."""
+        if other.device != self.device:
+            raise ValueError(f"sync_tables: the other table is on device {other.device}, this one on {self.device}")
+        n_rows = int(n_rows)
+        rf_self, rf_other = row_flags if isinstance(row_flags, (tuple, list)) else (row_flags, row_flags)
+        arr_a, ptr_a, mem_a = self._row_flags_arg(rf_self, n_rows)
+        arr_b, ptr_b, mem_b = self._row_flags_arg(rf_other, n_rows)
+        if ptr_a is not None and ptr_b is not None and mem_a != mem_b:
+            raise ValueError("sync_tables: both row_flags arrays must live in the same memory (host or device)")
+        mem = mem_a if ptr_a is not None else mem_b
+        res_a, res_b = CrdtResult(), CrdtResult()
+        st = self._lib.crdt_sync_tables(self._ctx, other._ctx, n_rows, int(since_self), int(since_other), int(wall),
+                                        ptr_a, ptr_b, mem, ctypes.byref(res_a), ctypes.byref(res_b))
+        self._check(st, "crdt_sync_tables")
+        if rf_self is True:
+            arr_a = arr_a[:n_rows]
+        if rf_other is True:
+            arr_b = arr_b[:n_rows]
+        return (res_a.as_dict(), arr_a), (res_b.as_dict(), arr_b)
 
     def clear_rows(self, first: int, count: int):
         self._check(self._lib.crdt_clear_rows(self._ctx, first, count), "crdt_clear_rows")
@@ -437,7 +468,8 @@ class DeviceTable:
                   "high_water": 64, "anchored": 128, "wire_packed": 256, "own_in_place": 512,
                   "flagged": 1024, "ordered": 2048,
                   "combined": 4096, "route_l1": 8192, "route_tuned": 16384, "rl1_head": 262144,
-                  "compact": 524288, "hot_direct": 1048576, "table": 2097152}
+                  "compact": 524288, "hot_direct": 1048576, "table": 2097152,
+                  "sync": 4194304}
 
     def last_plan(self) -> dict:
         """crdt_last_plan: how the last merge ran ({'sorted': bool, 'packed': ..., ...})."""

@@ -260,6 +260,41 @@ int crdt_merge(crdt_ctx* ctx, const crdt_batch* batch, int64_t wall_millis, uint
 int crdt_merge_table(crdt_ctx* dst, crdt_ctx* src, uint64_t n_rows, int64_t since_lt, int64_t wall_millis,
                      uint8_t* row_flags, int32_t flags_mem, crdt_result* out);
 
+/* The two-replica exchange a.merge(b.recordMap(modifiedSince: since_b)); b.merge(a.recordMap(modifiedSince:
+ * since_a)) for two ctxs on the SAME device sharing one key / node / value interning.  For every input it
+ * leaves exactly what
+ *     s1 = crdt_merge_table(a, b, n_rows, since_b, wall_millis, flags_a, flags_mem, out_a);
+ *     if (s1 == 0) s2 = crdt_merge_table(b, a, n_rows, since_a, wall_millis, flags_b, flags_mem, out_b);
+ * leaves: both tables' rows and canonicals, every field of both crdt_results, both row-flag arrays
+ * ([n_rows] bytes each, indexed by ROW id, every entry written) and both ctxs' export views untouched.  The
+ * second merge selects from a AS THE FIRST LEFT IT: a row of b that won into a carries mod = a's canonical
+ * after its recv loop and goes back to b's merge (where it loses the tie unless b's row is invisible).
+ * s1 != 0 (an exception in a.merge ends the exchange, as in Dart, or an error): b is untouched, *out_b is
+ * zero except exc_index = UINT64_MAX and canonical_lt = b's canonical, flags_b (if given) is all zero, and
+ * the call returns s1.  Otherwise it returns s2; a negative s2 (an error in the second merge) leaves a
+ * MERGED: step 1 is not undone.
+ * The win decision (crdt.dart:83-84) reads no canonical clock, so both directions are decided on one read
+ * of the two rows: a clock pass over {lt, rank, mod} of both tables (each tile's rows selected either way,
+ * two selection bits per row, and per direction the selection's max lt, largest id, count and whether a row
+ * may raise in recv()), one read-back of eight words, and an apply pass that skips the tiles holding no
+ * selected row, loads both rows of the selected ones and stores the winners on each side (a with mod =
+ * a's canonical after its recv loop, b with b's).  Scratch, on a: the words, a count per tile and two bits
+ * per row; nothing grows with the selection.
+ * The call runs the composition above itself, nothing written by then, whenever a selected row may raise in
+ * either direction, step 1's closing Hlc.send raises, a's canonical after its recv loop is below since_a
+ * (step 1's winners would not be selected by step 2), a == b, either ctx is pinned to CRDT_PATH_SORTED, or
+ * either ctx was created under CRDT_TABLE_MERGE=0.  Step 2's Hlc.send raising after its store is reported
+ * in place (status 1 or 3 in *out_b and as the return value, both tables stored).
+ * CRDT_E_INVALID, nothing touched: a null ctx or out, n_rows above either capacity, different devices, a ctx
+ * joined to a communicator, a bad flags_mem with a flags pointer.  Neither ctx may be in another call; the
+ * work runs on a's stream after b's is drained, and the call is synchronous.  After the fused form
+ * crdt_last_plan of BOTH ctxs is CRDT_PLAN_TABLE | CRDT_PLAN_SYNC and crdt_last_path CRDT_PATH_GATHER (after
+ * a fallback: what the composition's calls report); crdt_timing is recorded on a: scan_ms (the clock
+ * pass), apply_ms (the apply pass) and total_ms. */
+int crdt_sync_tables(crdt_ctx* a, crdt_ctx* b, uint64_t n_rows, int64_t since_a, int64_t since_b,
+                     int64_t wall_millis, uint8_t* flags_a, uint8_t* flags_b, int32_t flags_mem,
+                     crdt_result* out_a, crdt_result* out_b);
+
 /* ---- key-sharded multi-GPU (north star config 4) -------------
  * n_ranks ctxs — one per GPU, normally one process per GPU — form ONE replica whose
  * keys are sharded: rank d owns key k iff k % n_ranks == d and stores it at slot
@@ -411,8 +446,10 @@ enum crdt_plan_flags {
     CRDT_PLAN_HOT_DIRECT = 1048576, /* the compact order-free form of a two-level table: level 1 wrote the records of
                                     the first CRDT_HOT_BUCKETS final buckets (keys < H * 4096) straight into their
                                     final bucket; they skipped level 2 (sorted_path.inc, HotL1) */
-    CRDT_PLAN_TABLE = 2097152     /* the last merge on this ctx was a crdt_merge_table that ran the fused table
+    CRDT_PLAN_TABLE = 2097152,    /* the last merge on this ctx was a crdt_merge_table that ran the fused table
                                     form (table_merge.inc); set alone */
+    CRDT_PLAN_SYNC = 4194304      /* ... or, with CRDT_PLAN_TABLE, one side of a crdt_sync_tables that ran its
+                                    fused two-way form (set on both ctxs) */
 };
 int crdt_last_plan(const crdt_ctx* ctx, uint32_t* flags);
 
