@@ -157,6 +157,28 @@ typedef long long i64x2 __attribute__((ext_vector_type(2)));
 __host__ __device__ inline int64_t wsub(int64_t a, int64_t b) { return (int64_t)((uint64_t)a - (uint64_t)b); }
 __host__ __device__ inline int64_t imax(int64_t a, int64_t b) { return a > b ? a : b; }
 
+// Hlc.send(R) at the wall (hlc.dart:51-74): drift is decided first, then counter overflow, else the new
+// canonical.  A send that raises leaves the canonical at R.
+struct HlcSend {
+    int32_t status;        // CRDT_OK, CRDT_CLOCK_DRIFT or CRDT_OVERFLOW
+    int64_t drift_ms;      // the drift where it raises ClockDrift, else 0
+    int64_t counter;       // the counter where it raises Overflow, else 0
+    int64_t canonical;
+    __host__ __device__ void into(crdt_result& res) const {
+        res.status = status;
+        res.drift_ms = drift_ms;
+        res.counter = counter;
+        res.canonical_lt = canonical;
+    }
+};
+__host__ __device__ inline HlcSend hlc_send(int64_t r, int64_t wall) {
+    const int64_t m = r >> kShift, mn = imax(m, wall);
+    const int64_t cn = (m == mn) ? (r & kMaxCounter) + 1 : 0;
+    if (wsub(mn, wall) > kMaxDrift) return {CRDT_CLOCK_DRIFT, wsub(mn, wall), 0, r};
+    if (cn > kMaxCounter) return {CRDT_OVERFLOW, 0, cn, r};
+    return {CRDT_OK, 0, 0, (int64_t)(((uint64_t)mn << kShift) + (uint64_t)cn)};
+}
+
 // ------------------------------------------------------------------ wave helpers
 __device__ inline int64_t wave_max(int64_t v) {
 #pragma unroll
@@ -526,13 +548,6 @@ __global__ __launch_bounds__(256) void k_tmax(const int64_t* __restrict__ T, con
 // so D_j = C_j - j = max(C_0, max_{k<=j}(max(M_k + 1, W) - k)) — a prefix max.
 // Also finds the first changeset whose send() raises (drift, then overflow).
 // =============================================================================
-__device__ inline bool send_fails(int64_t r, int64_t wall) {
-    const int64_t m = r >> kShift, c = r & kMaxCounter;
-    const int64_t mn = imax(m, wall);
-    const int64_t cn = (m == mn) ? c + 1 : 0;
-    return wsub(mn, wall) > kMaxDrift || cn > kMaxCounter;
-}
-
 // kTiles (small batches: <= kClockTilesMax tiles, R <= kClockRMax): M_j is reduced here from the
 // scan's tile maxima T (LDS max per changeset) instead of by a separate k_tmax launch.
 constexpr uint32_t kClockTilesMax = 8192;         // <= 8 tiles per thread (cfg3's 24K tiles: k_tmax is faster)
@@ -609,7 +624,7 @@ __global__ __launch_bounds__(1024) void k_clock(
             Cprev[j] = cprev;
             Rj[j] = r;
             Cj[j] = ccur;
-            if (send_fails(r, wall)) first = first < j ? first : j;
+            if (hlc_send(r, wall).status != CRDT_OK) first = first < j ? first : j;
         }
         carry = imax(carry, total);
         __syncthreads();
@@ -672,17 +687,7 @@ __device__ void resolve_body(const long long* __restrict__ event, uint32_t R, in
         res.exc_changeset = j;
         if (low == kLowMask) {                       // send() after storing changeset j
             stop = j + 1;
-            const int64_t r = Rj[j];
-            const int64_t m = r >> kShift, c = r & kMaxCounter;
-            const int64_t mn = imax(m, wall);
-            res.canonical_lt = r;
-            if (wsub(mn, wall) > kMaxDrift) {
-                res.status = CRDT_CLOCK_DRIFT;
-                res.drift_ms = wsub(mn, wall);
-            } else {
-                res.status = CRDT_OVERFLOW;
-                res.counter = c + 1;
-            }
+            hlc_send(Rj[j], wall).into(res);         // (k_clock found that it raises)
         } else {                                     // recv() inside changeset j
             stop = j;
             res.exc_index = (uint64_t)low;
@@ -2231,6 +2236,15 @@ int reset_misc(crdt_ctx* c) {
     return CRDT_OK;
 }
 
+// A result that reports nothing stored and no exception, with the canonical as given.
+crdt_result cleared_result(int64_t canonical) {
+    crdt_result res;
+    memset(&res, 0, sizeof(res));
+    res.exc_index = UINT64_MAX;
+    res.canonical_lt = canonical;
+    return res;
+}
+
 // HIP events of a timed call: start, after the scan, after the clock phase (and its collectives),
 // apply start (route_ms = the gap before it), end; then one pair per sampled apply window.
 constexpr size_t kEvStart = 0, kEvScan = 1, kEvClock = 2, kEvApply = 3, kEvEnd = 4;
@@ -3766,29 +3780,17 @@ int crdt_put_rows(crdt_ctx* c, const uint32_t* key_id, const int64_t* lt, const 
 int crdt_put_stamped(crdt_ctx* c, const uint32_t* key_id, const uint32_t* val, uint64_t n, int64_t wall,
                      int32_t mem, crdt_result* out) {
     if (!c) return CRDT_E_INVALID;
-    crdt_result res;
-    memset(&res, 0, sizeof(res));
-    res.exc_index = UINT64_MAX;
-    res.canonical_lt = c->canonical;
+    crdt_result res = cleared_result(c->canonical);
     if (n == 0) { if (out) *out = res; return CRDT_OK; }     // crdt.dart:48
     if (!key_id || !val) return CRDT_E_INVALID;
-    // Hlc.send (hlc.dart:51-74), once for the whole call (crdt.dart:40, 50)
-    const int64_t cm = c->canonical >> kShift, cc = c->canonical & kMaxCounter;
-    const int64_t mn = imax(cm, wall);
-    const int64_t cn = (cm == mn) ? cc + 1 : 0;
-    if (wsub(mn, wall) > kMaxDrift) {
-        res.status = CRDT_CLOCK_DRIFT;
-        res.drift_ms = wsub(mn, wall);
+    // Hlc.send, once for the whole call (crdt.dart:40, 50): it raises before any row is stored
+    const HlcSend send = hlc_send(c->canonical, wall);
+    if (send.status != CRDT_OK) {
+        send.into(res);
         if (out) *out = res;
         return res.status;
     }
-    if (cn > kMaxCounter) {
-        res.status = CRDT_OVERFLOW;
-        res.counter = cn;
-        if (out) *out = res;
-        return res.status;
-    }
-    const int64_t stamp = (int64_t)(((uint64_t)mn << kShift) + (uint64_t)cn);
+    const int64_t stamp = send.canonical;
     HIPCHK(hipSetDevice(c->device));
     const uint32_t *dk, *dv;
     int st;
@@ -4031,11 +4033,7 @@ int crdt_merge(crdt_ctx* c, const crdt_batch* batch, int64_t wall, uint8_t* win_
     if (st) return st;
     const uint32_t R = batch->n_changesets;
     if (R == 0) {                                            // no merge() call at all
-        crdt_result res;
-        memset(&res, 0, sizeof(res));
-        res.exc_index = UINT64_MAX;
-        res.canonical_lt = c->canonical;
-        if (out) *out = res;
+        if (out) *out = cleared_result(c->canonical);
         return CRDT_OK;
     }
     HIPCHK(hipSetDevice(c->device));
@@ -4108,6 +4106,102 @@ int crdt_merge(crdt_ctx* c, const crdt_batch* batch, int64_t wall, uint8_t* win_
     return st;
 }
 
+// ---- The host steps that the fused table forms (crdt_merge_table, crdt_sync_tables) share.  c is the ctx
+// whose stream and scratch the call runs on; dirs is the number of merge directions (1 or 2), each with
+// kTmWords clock words and one mask bit per row.
+static bool tm_args_ok(const crdt_ctx* x, const crdt_ctx* y, bool flags, int32_t flags_mem) {
+    return x && y && x->device == y->device && !x->has_comm && !y->has_comm &&
+           (!flags || flags_mem == CRDT_MEM_HOST || flags_mem == CRDT_MEM_DEVICE);
+}
+
+// Where the kernels write a flag array: the caller's device memory, or c's staging buffer for host memory.
+static int tm_stage_flags(crdt_ctx* c, uint8_t* flags, int32_t flags_mem, uint64_t n_rows, uint8_t** dev) {
+    *dev = flags;
+    if (flags && flags_mem == CRDT_MEM_HOST) {
+        HIPALLOC(c->s_flags.ensure(n_rows ? n_rows : 1));
+        *dev = c->s_flags.p;
+    }
+    return CRDT_OK;
+}
+
+static int tm_flags_to_host(crdt_ctx* c, uint8_t* flags, const uint8_t* dev, int32_t flags_mem, uint64_t n_rows) {
+    if (flags && flags_mem == CRDT_MEM_HOST && n_rows)
+        HIPCHK(hipMemcpyAsync(flags, dev, n_rows, hipMemcpyDeviceToHost, c->stream));
+    return CRDT_OK;
+}
+
+// The scratch of nb tiles, the call's timing state, the start event, and the clock words zeroed.
+static int tm_begin(crdt_ctx* c, unsigned nb, int dirs) {
+    HIPALLOC(c->t_words.ensure(kTmWords * dirs));
+    HIPALLOC(c->t_sel.ensure(nb ? nb : 1));
+    HIPALLOC(c->t_mask.ensure(nb ? (size_t)nb * kTmMaskWords * dirs : 1));
+    if (c->timing) HIPCHK(ensure_events(c, events_for(1)));
+    c->windows.clear();
+    c->apply_total = 0;
+    c->sent_bytes = 0;
+    ev_record(c, kEvStart);
+    HIPCHK(hipMemsetAsync(c->t_words.p, 0, kTmWords * dirs * sizeof(unsigned long long), c->stream));
+    return CRDT_OK;
+}
+
+// After the clock pass: its words on the host.
+static int tm_read_words(crdt_ctx* c, unsigned long long* w, int dirs) {
+    ev_record(c, kEvScan);
+    HIPCHK(hipMemcpyAsync(w, c->t_words.p, kTmWords * dirs * sizeof(*w), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return CRDT_OK;
+}
+
+// The canonical that the recv loop over one direction's selection leaves (crdt.dart:82): max(C, its largest
+// lt).  w: that direction's clock words.
+static int64_t tm_recv_canonical(int64_t c, const unsigned long long* w) {
+    return w[3] ? imax(c, (int64_t)(w[0] ^ (1ull << 63))) : c;
+}
+
+// The apply pass writes the flag of every row it covers, [0, covered); the host zeroes the rest.
+static int tm_zero_uncovered(crdt_ctx* c, uint8_t* rf, uint64_t covered, uint64_t n_rows) {
+    if (rf && n_rows > covered) HIPCHK(hipMemsetAsync(rf + covered, 0, n_rows - covered, c->stream));
+    return CRDT_OK;
+}
+
+// The events around the apply launch (has: there is one), which a timed call reports as one window.
+static void tm_apply_begin(crdt_ctx* c, bool has) {
+    ev_record(c, kEvApply);
+    if (has) ev_record(c, ev_window(0, false));
+}
+
+static void tm_apply_end(crdt_ctx* c, bool has) {
+    if (has) {
+        ev_record(c, ev_window(0, true));
+        if (c->timing) c->windows.push_back(1u);
+        c->apply_total = 1;
+    }
+    ev_record(c, kEvEnd);
+}
+
+// After the apply pass: Misc on the host, and everything queued on the stream done.
+static int tm_read_misc(crdt_ctx* c) {
+    HIPCHK(hipMemcpyAsync(c->h_misc, c->d_misc, sizeof(Misc), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return CRDT_OK;
+}
+
+// One direction's end: its counts from the striped slots [first, first + count), and on its receiving ctx
+// the high-water mark (every row written is a selected one; w: the direction's clock words), the new
+// canonical and what crdt_last_plan reports.
+static void tm_finish(crdt_ctx* c, crdt_result* res, const Misc* m, int first, int count,
+                      const unsigned long long* w, bool sync) {
+    for (int s = first; s < first + count; ++s) {
+        res->n_present += m->present[s];
+        res->n_won += m->won[s];
+    }
+    if (w[3]) raise_hw(c, w[1]);
+    c->canonical = res->canonical_lt;
+    c->last_table = true;
+    c->last_sync = sync;
+    c->last_sorted = false;
+}
+
 // ---- crdt_merge_table: dst.merge(src.recordMap(modifiedSince)) over two aligned tables (table_merge.inc)
 // The composition itself: export src's selection, merge it into dst as one device changeset, carry the
 // per-record win flags to their row ids.  Exact by construction; the fused form falls back to it whenever
@@ -4144,19 +4238,16 @@ static int table_merge_composed(crdt_ctx* dst, crdt_ctx* src, uint64_t n_rows, i
     const crdt_batch b = {v.key_id, v.lt, v.rank, v.val, nullptr, offs, 1, CRDT_MEM_DEVICE};
     st = crdt_merge(dst, &b, wall, wf, out);
     if (row_flags && n_rows && (st >= 0 || st == CRDT_E_KEY_RANGE)) {
-        uint8_t* rf = row_flags;
-        if (flags_mem == CRDT_MEM_HOST) {
-            HIPALLOC(dst->s_flags.ensure(n_rows));
-            rf = dst->s_flags.p;
-        }
+        uint8_t* rf;
+        int fst;
+        if ((fst = tm_stage_flags(dst, row_flags, flags_mem, n_rows, &rf))) return fst;
         HIPCHK(hipMemsetAsync(rf, 0, n_rows, dst->stream));
         if (v.n) {
             k_tm_flags_scatter<<<std::min<uint32_t>(grid_for(v.n, 256), 8192), 256, 0, dst->stream>>>(
                 v.key_id, wf, v.n, n_rows, rf);
             HIPCHK(hipGetLastError());
         }
-        if (flags_mem == CRDT_MEM_HOST)
-            HIPCHK(hipMemcpyAsync(row_flags, rf, n_rows, hipMemcpyDeviceToHost, dst->stream));
+        if ((fst = tm_flags_to_host(dst, row_flags, rf, flags_mem, n_rows))) return fst;
         HIPCHK(hipStreamSynchronize(dst->stream));
     }
     return st;
@@ -4164,10 +4255,7 @@ static int table_merge_composed(crdt_ctx* dst, crdt_ctx* src, uint64_t n_rows, i
 
 int crdt_merge_table(crdt_ctx* dst, crdt_ctx* src, uint64_t n_rows, int64_t since_lt, int64_t wall,
                      uint8_t* row_flags, int32_t flags_mem, crdt_result* out) {
-    if (!dst || !src || !out || n_rows > src->cap || dst->device != src->device || dst->has_comm ||
-        src->has_comm)
-        return CRDT_E_INVALID;
-    if (row_flags && flags_mem != CRDT_MEM_HOST && flags_mem != CRDT_MEM_DEVICE) return CRDT_E_INVALID;
+    if (!tm_args_ok(dst, src, row_flags != nullptr, flags_mem) || !out || n_rows > src->cap) return CRDT_E_INVALID;
     HIPCHK(hipSetDevice(dst->device));
     if (dst->env_dynamic) read_env_knobs(dst);
     // the composition: switched to, a self-merge (the passes would read rows they write), or a ctx whose
@@ -4177,88 +4265,44 @@ int crdt_merge_table(crdt_ctx* dst, crdt_ctx* src, uint64_t n_rows, int64_t sinc
     HIPCHK(hipStreamSynchronize(src->stream));        // src's rows are final before dst's stream reads them
     const uint64_t rows = ex_rows(src, n_rows, since_lt);
     const unsigned nb = grid_for(rows, kTmTile);
-    HIPALLOC(dst->t_words.ensure(4));
-    HIPALLOC(dst->t_sel.ensure(nb ? nb : 1));
-    HIPALLOC(dst->t_mask.ensure(nb ? (size_t)nb * kTmMaskWords : 1));
-    uint8_t* rf = row_flags;
-    if (row_flags && flags_mem == CRDT_MEM_HOST) {
-        HIPALLOC(dst->s_flags.ensure(n_rows ? n_rows : 1));
-        rf = dst->s_flags.p;
-    }
-    if (dst->timing) HIPCHK(ensure_events(dst, events_for(1)));
-    dst->windows.clear();
-    dst->apply_total = 0;
-    dst->sent_bytes = 0;
-    ev_record(dst, kEvStart);
+    uint8_t* rf;
+    int st;
+    if ((st = tm_stage_flags(dst, row_flags, flags_mem, n_rows, &rf))) return st;
+    if ((st = tm_begin(dst, nb, 1))) return st;
     // pass 1: the clock words of src's selection
     const int64_t c0 = dst->canonical;
-    HIPCHK(hipMemsetAsync(dst->t_words.p, 0, 4 * sizeof(unsigned long long), dst->stream));
     if (rows) {
         k_tm_clock<<<std::min(nb, kTmClockGrid), kTmThreads, 0, dst->stream>>>(
             src->table, rows, since_lt, nb, c0, wall, dst->local_rank, dst->t_sel.p, dst->t_mask.p, dst->t_words.p);
         HIPCHK(hipGetLastError());
     }
-    ev_record(dst, kEvScan);
-    unsigned long long w[4] = {0, 0, 0, 0};
-    HIPCHK(hipMemcpyAsync(w, dst->t_words.p, sizeof(w), hipMemcpyDeviceToHost, dst->stream));
-    HIPCHK(hipStreamSynchronize(dst->stream));
+    unsigned long long w[kTmWords] = {};
+    if ((st = tm_read_words(dst, w, 1))) return st;
     const bool has = w[3] != 0;
     // a selected row may raise in recv(), or lies outside dst: nothing is written yet, the composition
     // gives the exact stop point, exception details and error
     if (w[2] || (has && w[1] > dst->cap))
         return table_merge_composed(dst, src, n_rows, since_lt, wall, row_flags, flags_mem, out);
-    // the recv loop leaves R = max(C_0, M) (crdt.dart:82); the rows are stored with mod = R, then
-    // Hlc.send(R) (hlc.dart:51-74, crdt.dart:93) fixes the canonical or raises after the store
-    const int64_t R = has ? imax(c0, (int64_t)(w[0] ^ (1ull << 63))) : c0;
-    crdt_result res;
-    memset(&res, 0, sizeof(res));
-    res.exc_index = UINT64_MAX;
+    // the recv loop leaves R; the rows are stored with mod = R, then Hlc.send(R) (crdt.dart:93) fixes the
+    // canonical or raises after the store
+    const int64_t R = tm_recv_canonical(c0, w);
+    crdt_result res = cleared_result(c0);
     res.n_stored = 1;
-    const int64_t rm = R >> kShift, rc = R & kMaxCounter;
-    const int64_t mn = imax(rm, wall);
-    const int64_t cn = (rm == mn) ? rc + 1 : 0;
-    if (wsub(mn, wall) > kMaxDrift) {
-        res.status = CRDT_CLOCK_DRIFT;
-        res.drift_ms = wsub(mn, wall);
-        res.canonical_lt = R;
-    } else if (cn > kMaxCounter) {
-        res.status = CRDT_OVERFLOW;
-        res.counter = cn;
-        res.canonical_lt = R;
-    } else {
-        res.canonical_lt = (int64_t)(((uint64_t)mn << kShift) + (uint64_t)cn);
-    }
+    hlc_send(R, wall).into(res);
     ev_record(dst, kEvClock);
     // pass 2: the winners into dst
-    int st;
     if ((st = reset_misc(dst))) return st;
-    // the apply pass writes the flag of every row it covers, [0, rows); the host zeroes the rest
-    const uint64_t covered = has ? rows : 0;
-    if (rf && n_rows > covered) HIPCHK(hipMemsetAsync(rf + covered, 0, n_rows - covered, dst->stream));
-    ev_record(dst, kEvApply);
+    if ((st = tm_zero_uncovered(dst, rf, has ? rows : 0, n_rows))) return st;
+    tm_apply_begin(dst, has);
     if (has) {
-        ev_record(dst, ev_window(0, false));
         k_tm_apply<<<nb, kTmThreads, 0, dst->stream>>>(src->table, dst->table, rows, dst->cap, dst->t_sel.p,
                                                        dst->t_mask.p, R, dst->d_misc, rf);
         HIPCHK(hipGetLastError());
-        ev_record(dst, ev_window(0, true));
-        if (dst->timing) dst->windows.push_back(1u);
-        dst->apply_total = 1;
     }
-    ev_record(dst, kEvEnd);
-    HIPCHK(hipMemcpyAsync(dst->h_misc, dst->d_misc, sizeof(Misc), hipMemcpyDeviceToHost, dst->stream));
-    if (row_flags && flags_mem == CRDT_MEM_HOST && n_rows)
-        HIPCHK(hipMemcpyAsync(row_flags, rf, n_rows, hipMemcpyDeviceToHost, dst->stream));
-    HIPCHK(hipStreamSynchronize(dst->stream));
-    for (int s = 0; s < kCounterSlots; ++s) {
-        res.n_present += dst->h_misc->present[s];
-        res.n_won += dst->h_misc->won[s];
-    }
-    if (has) raise_hw(dst, w[1]);                     // every row written is a selected one
-    dst->canonical = res.canonical_lt;
-    dst->last_table = true;
-    dst->last_sync = false;
-    dst->last_sorted = false;
+    tm_apply_end(dst, has);
+    if ((st = tm_flags_to_host(dst, row_flags, rf, flags_mem, n_rows))) return st;
+    if ((st = tm_read_misc(dst))) return st;
+    tm_finish(dst, &res, dst->h_misc, 0, kCounterSlots, w, false);
     collect_timing(dst);
     *out = res;
     return res.status;
@@ -4273,9 +4317,7 @@ static int sync_tables_composed(crdt_ctx* a, crdt_ctx* b, uint64_t n_rows, int64
                                 crdt_result* out_a, crdt_result* out_b) {
     const int s1 = crdt_merge_table(a, b, n_rows, since_b, wall, flags_a, flags_mem, out_a);
     if (s1 == 0) return crdt_merge_table(b, a, n_rows, since_a, wall, flags_b, flags_mem, out_b);
-    memset(out_b, 0, sizeof(*out_b));
-    out_b->exc_index = UINT64_MAX;
-    out_b->canonical_lt = b->canonical;
+    *out_b = cleared_result(b->canonical);
     if (flags_b && n_rows) {
         if (flags_mem == CRDT_MEM_HOST) {
             memset(flags_b, 0, n_rows);
@@ -4287,32 +4329,11 @@ static int sync_tables_composed(crdt_ctx* a, crdt_ctx* b, uint64_t n_rows, int64
     return s1;
 }
 
-// Hlc.send(R) at the wall (hlc.dart:51-74) into res: the canonical it leaves, or the exception it raises
-// after the store (crdt.dart:93), as crdt_merge_table evaluates it.
-static void sync_send(int64_t R, int64_t wall, crdt_result* res) {
-    const int64_t rm = R >> kShift, rc = R & kMaxCounter;
-    const int64_t mn = imax(rm, wall);
-    const int64_t cn = (rm == mn) ? rc + 1 : 0;
-    if (wsub(mn, wall) > kMaxDrift) {
-        res->status = CRDT_CLOCK_DRIFT;
-        res->drift_ms = wsub(mn, wall);
-        res->canonical_lt = R;
-    } else if (cn > kMaxCounter) {
-        res->status = CRDT_OVERFLOW;
-        res->counter = cn;
-        res->canonical_lt = R;
-    } else {
-        res->canonical_lt = (int64_t)(((uint64_t)mn << kShift) + (uint64_t)cn);
-    }
-}
-
 int crdt_sync_tables(crdt_ctx* a, crdt_ctx* b, uint64_t n_rows, int64_t since_a, int64_t since_b, int64_t wall,
                      uint8_t* flags_a, uint8_t* flags_b, int32_t flags_mem, crdt_result* out_a,
                      crdt_result* out_b) {
-    if (!a || !b || !out_a || !out_b || n_rows > a->cap || n_rows > b->cap || a->device != b->device ||
-        a->has_comm || b->has_comm)
+    if (!tm_args_ok(a, b, flags_a || flags_b, flags_mem) || !out_a || !out_b || n_rows > a->cap || n_rows > b->cap)
         return CRDT_E_INVALID;
-    if ((flags_a || flags_b) && flags_mem != CRDT_MEM_HOST && flags_mem != CRDT_MEM_DEVICE) return CRDT_E_INVALID;
     HIPCHK(hipSetDevice(a->device));
     if (a->env_dynamic) read_env_knobs(a);
     if (b->env_dynamic) read_env_knobs(b);
@@ -4323,88 +4344,50 @@ int crdt_sync_tables(crdt_ctx* a, crdt_ctx* b, uint64_t n_rows, int64_t since_a,
     HIPCHK(hipStreamSynchronize(b->stream));          // b's rows are final before a's stream reads and writes them
     const uint64_t rows = std::max(ex_rows(a, n_rows, since_a), ex_rows(b, n_rows, since_b));
     const unsigned nb = grid_for(rows, kTmTile);
-    HIPALLOC(a->t_words.ensure(kSyWords));
-    HIPALLOC(a->t_sel.ensure(nb ? nb : 1));
-    HIPALLOC(a->t_mask.ensure(nb ? (size_t)nb * kTmMaskWords * 2 : 1));
-    uint8_t *rfa = flags_a, *rfb = flags_b;
-    if (flags_mem == CRDT_MEM_HOST) {
-        if (flags_a) { HIPALLOC(a->s_flags.ensure(n_rows ? n_rows : 1)); rfa = a->s_flags.p; }
-        if (flags_b) { HIPALLOC(b->s_flags.ensure(n_rows ? n_rows : 1)); rfb = b->s_flags.p; }
-    }
-    if (a->timing) HIPCHK(ensure_events(a, events_for(1)));
-    a->windows.clear();
-    a->apply_total = 0;
-    a->sent_bytes = 0;
-    ev_record(a, kEvStart);
-    // pass 1: the clock words of both directions
+    uint8_t *rfa, *rfb;
+    int st;
+    if ((st = tm_stage_flags(a, flags_a, flags_mem, n_rows, &rfa))) return st;
+    if ((st = tm_stage_flags(b, flags_b, flags_mem, n_rows, &rfb))) return st;
+    if ((st = tm_begin(a, nb, 2))) return st;
+    // pass 1: the clock words of both directions (direction 1 in w[0..3], direction 2 in w[4..7])
     const int64_t ca = a->canonical, cb = b->canonical;
-    HIPCHK(hipMemsetAsync(a->t_words.p, 0, kSyWords * sizeof(unsigned long long), a->stream));
     if (rows) {
         k_sy_clock<<<std::min(nb, kSyClockGrid), kTmThreads, 0, a->stream>>>(
             a->table, b->table, rows, since_a, since_b, nb, ca, cb, wall, a->local_rank, b->local_rank, a->t_sel.p,
             a->t_mask.p, a->t_words.p);
         HIPCHK(hipGetLastError());
     }
-    ev_record(a, kEvScan);
     unsigned long long w[kSyWords] = {};
-    HIPCHK(hipMemcpyAsync(w, a->t_words.p, sizeof(w), hipMemcpyDeviceToHost, a->stream));
-    HIPCHK(hipStreamSynchronize(a->stream));
-    const bool has1 = w[3] != 0, has2 = w[7] != 0;
-    // the recv loops leave R_a = max(C_a, M_b) and R_b = max(C_b, M_a') (crdt.dart:82)
-    const int64_t Ra = has1 ? imax(ca, (int64_t)(w[0] ^ (1ull << 63))) : ca;
-    const int64_t Rb = has2 ? imax(cb, (int64_t)(w[4] ^ (1ull << 63))) : cb;
-    crdt_result ra, rb;
-    memset(&ra, 0, sizeof(ra));
-    memset(&rb, 0, sizeof(rb));
-    ra.exc_index = rb.exc_index = UINT64_MAX;
+    if ((st = tm_read_words(a, w, 2))) return st;
+    // the recv loops leave R_a = max(C_a, M_b) and R_b = max(C_b, M_a'); each side's Hlc.send follows its store
+    const int64_t Ra = tm_recv_canonical(ca, w), Rb = tm_recv_canonical(cb, w + kTmWords);
+    crdt_result ra = cleared_result(ca), rb = cleared_result(cb);
     ra.n_stored = rb.n_stored = 1;
-    sync_send(Ra, wall, &ra);
-    sync_send(Rb, wall, &rb);
+    hlc_send(Ra, wall).into(ra);
+    hlc_send(Rb, wall).into(rb);
     // a row may raise in either recv(), step 1's send() raises (the exchange ends there), or step 1's
     // winners, stamped mod = R_a, would not be selected by since_a (direction 2's words assumed they are):
     // nothing is written yet, the composition gives the exact stop points and exception details
-    if (w[2] || w[6] || ra.status != CRDT_OK || Ra < since_a)
+    if (w[2] || w[kTmWords + 2] || ra.status != CRDT_OK || Ra < since_a)
         return sync_tables_composed(a, b, n_rows, since_a, since_b, wall, flags_a, flags_b, flags_mem, out_a, out_b);
     ev_record(a, kEvClock);
     // pass 2: the winners into both tables (step 2's send() raising after its store stays in place)
-    int st;
     if ((st = reset_misc(a))) return st;
-    const bool has = has1 || has2;
-    const uint64_t covered = has ? rows : 0;          // the apply pass writes the flags of [0, rows)
-    if (n_rows > covered) {
-        if (rfa) HIPCHK(hipMemsetAsync(rfa + covered, 0, n_rows - covered, a->stream));
-        if (rfb) HIPCHK(hipMemsetAsync(rfb + covered, 0, n_rows - covered, a->stream));
-    }
-    ev_record(a, kEvApply);
+    const bool has = w[3] || w[kTmWords + 3];         // rows selected in either direction
+    if ((st = tm_zero_uncovered(a, rfa, has ? rows : 0, n_rows))) return st;
+    if ((st = tm_zero_uncovered(a, rfb, has ? rows : 0, n_rows))) return st;
+    tm_apply_begin(a, has);
     if (has) {
-        ev_record(a, ev_window(0, false));
         k_sy_apply<<<nb, kTmThreads, 0, a->stream>>>(a->table, b->table, rows, a->t_sel.p, a->t_mask.p, Ra, Rb,
                                                      a->d_misc, rfa, rfb);
         HIPCHK(hipGetLastError());
-        ev_record(a, ev_window(0, true));
-        if (a->timing) a->windows.push_back(1u);
-        a->apply_total = 1;
     }
-    ev_record(a, kEvEnd);
-    HIPCHK(hipMemcpyAsync(a->h_misc, a->d_misc, sizeof(Misc), hipMemcpyDeviceToHost, a->stream));
-    if (flags_mem == CRDT_MEM_HOST && n_rows) {
-        if (flags_a) HIPCHK(hipMemcpyAsync(flags_a, rfa, n_rows, hipMemcpyDeviceToHost, a->stream));
-        if (flags_b) HIPCHK(hipMemcpyAsync(flags_b, rfb, n_rows, hipMemcpyDeviceToHost, a->stream));
-    }
-    HIPCHK(hipStreamSynchronize(a->stream));
-    for (int s = 0; s < kCounterSlots / 2; ++s) {
-        ra.n_present += a->h_misc->present[s];
-        ra.n_won += a->h_misc->won[s];
-        rb.n_present += a->h_misc->present[kCounterSlots / 2 + s];
-        rb.n_won += a->h_misc->won[kCounterSlots / 2 + s];
-    }
-    if (has1) raise_hw(a, w[1]);                      // every row written is a selected one, on either side
-    if (has2) raise_hw(b, w[5]);
-    a->canonical = ra.canonical_lt;
-    b->canonical = rb.canonical_lt;
-    a->last_table = b->last_table = true;
-    a->last_sync = b->last_sync = true;
-    a->last_sorted = b->last_sorted = false;
+    tm_apply_end(a, has);
+    if ((st = tm_flags_to_host(a, flags_a, rfa, flags_mem, n_rows))) return st;
+    if ((st = tm_flags_to_host(a, flags_b, rfb, flags_mem, n_rows))) return st;
+    if ((st = tm_read_misc(a))) return st;
+    tm_finish(a, &ra, a->h_misc, 0, kCounterSlots / 2, w, true);
+    tm_finish(b, &rb, a->h_misc, kCounterSlots / 2, kCounterSlots / 2, w + kTmWords, true);
     collect_timing(a);
     *out_a = ra;
     *out_b = rb;
