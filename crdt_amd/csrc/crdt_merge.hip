@@ -1857,9 +1857,12 @@ struct crdt_ctx {
     DBuf<uint32_t> t_sel;
     DBuf<unsigned long long> t_words, t_mask;
     DBuf<uint8_t> t_wflags;
+    DBuf<uint8_t> t_fstep, t_fmask;    // crdt_fanin_tables' composition: one step's row flags, a host mask's staging
+    DBuf<unsigned long long> t_fcounts; // its fused form: the sources' striped n_present / n_won (k_fan_apply)
     bool table_merge = true;           // CRDT_TABLE_MERGE=0: every crdt_merge_table takes the composition
     bool last_table = false;           // the last merge on this ctx ran the fused table form
     bool last_sync = false;            // ... as one side of a fused crdt_sync_tables
+    bool last_fanin = false;           // ... as the destination of a fused crdt_fanin_tables
     DBuf<long long> d_word;
     DBuf<unsigned long long> d_ibase;
     // per-call plan (set by scan, used by later phases)
@@ -3643,6 +3646,7 @@ void crdt_destroy(crdt_ctx* c) {
     c->x_key.release(); c->x_rank.release(); c->x_val.release(); c->x_lt.release(); c->x_mod.release();
     c->x_counts.release(); c->x_offs.release(); c->x_words.release();
     c->t_sel.release(); c->t_words.release(); c->t_mask.release(); c->t_wflags.release();
+    c->t_fstep.release(); c->t_fmask.release(); c->t_fcounts.release();
     c->d_word.release();
     c->d_ibase.release();
     c->p1_rec.release(); c->p1_kj.release(); c->p2_rec.release(); c->p2_kj.release();
@@ -4040,6 +4044,7 @@ int crdt_merge(crdt_ctx* c, const crdt_batch* batch, int64_t wall, uint8_t* win_
     if (c->env_dynamic) read_env_knobs(c);
     c->last_table = false;
     c->last_sync = false;
+    c->last_fanin = false;
     // rows >= hw_read are read as the fill by this merge; afterwards hw moves to hw_next (the
     // capacity unless finish_apply learned the batch's key bound) on every return path
     c->hw_read = (c->form_off & kFormNoHw) ? c->cap : c->hw;
@@ -4107,8 +4112,9 @@ int crdt_merge(crdt_ctx* c, const crdt_batch* batch, int64_t wall, uint8_t* win_
 }
 
 // ---- The host steps that the fused table forms (crdt_merge_table, crdt_sync_tables) share.  c is the ctx
-// whose stream and scratch the call runs on; dirs is the number of merge directions (1 or 2), each with
-// kTmWords clock words and one mask bit per row.
+// whose stream and scratch the call runs on; dirs is the number of merge directions (1, 2, or one per source
+// of crdt_fanin_tables), each with kTmWords clock words, one count per tile and one mask bit per row
+// (crdt_sync_tables' two directions share their tile counts).
 static bool tm_args_ok(const crdt_ctx* x, const crdt_ctx* y, bool flags, int32_t flags_mem) {
     return x && y && x->device == y->device && !x->has_comm && !y->has_comm &&
            (!flags || flags_mem == CRDT_MEM_HOST || flags_mem == CRDT_MEM_DEVICE);
@@ -4133,7 +4139,7 @@ static int tm_flags_to_host(crdt_ctx* c, uint8_t* flags, const uint8_t* dev, int
 // The scratch of nb tiles, the call's timing state, the start event, and the clock words zeroed.
 static int tm_begin(crdt_ctx* c, unsigned nb, int dirs) {
     HIPALLOC(c->t_words.ensure(kTmWords * dirs));
-    HIPALLOC(c->t_sel.ensure(nb ? nb : 1));
+    HIPALLOC(c->t_sel.ensure(nb ? (size_t)nb * dirs : 1));
     HIPALLOC(c->t_mask.ensure(nb ? (size_t)nb * kTmMaskWords * dirs : 1));
     if (c->timing) HIPCHK(ensure_events(c, events_for(1)));
     c->windows.clear();
@@ -4199,6 +4205,7 @@ static void tm_finish(crdt_ctx* c, crdt_result* res, const Misc* m, int first, i
     c->canonical = res->canonical_lt;
     c->last_table = true;
     c->last_sync = sync;
+    c->last_fanin = false;
     c->last_sorted = false;
 }
 
@@ -4394,6 +4401,142 @@ int crdt_sync_tables(crdt_ctx* a, crdt_ctx* b, uint64_t n_rows, int64_t since_a,
     return rb.status;
 }
 
+// ---- crdt_fanin_tables: for j < n_src: dst.merge(srcs[j].recordMap(since_j)) (table_merge.inc)
+// The composition itself: the crdt_merge_table calls of the contract, in call order, until one returns
+// non-zero; each step's row flags go into bit j of the mask.  Exact by construction; the fused form falls
+// back to it, with nothing written yet, whenever anything in the sequence may raise.
+static int fanin_tables_composed(crdt_ctx* dst, crdt_ctx* const* srcs, const int64_t* since, uint32_t n_src,
+                                 uint64_t n_rows, int64_t wall, uint8_t* win_mask, int32_t mask_mem,
+                                 crdt_result* out) {
+    uint8_t* step = nullptr;
+    uint8_t* wm = win_mask;
+    if (win_mask) {
+        HIPALLOC(dst->t_fstep.ensure(n_rows ? n_rows : 1));
+        step = dst->t_fstep.p;
+        if (mask_mem == CRDT_MEM_HOST) {
+            HIPALLOC(dst->t_fmask.ensure(n_rows ? n_rows : 1));
+            wm = dst->t_fmask.p;
+        }
+        if (n_rows) HIPCHK(hipMemsetAsync(wm, 0, n_rows, dst->stream));
+    }
+    int st = CRDT_OK;
+    for (uint32_t j = 0; j < n_src; ++j) {
+        st = crdt_merge_table(dst, srcs[j], n_rows, since[j], wall, step, CRDT_MEM_DEVICE, &out[j]);
+        if (st >= 0 && win_mask && n_rows) {                  // (an error stores nothing: no bit)
+            k_fan_or_flags<<<std::min<uint32_t>(grid_for(n_rows, 256), 8192), 256, 0, dst->stream>>>(step, n_rows, j, wm);
+            HIPCHK(hipGetLastError());
+        }
+        if (st != 0) {                                        // an exception (or an error) ends the sequence
+            for (uint32_t k = j + 1; k < n_src; ++k) out[k] = cleared_result(dst->canonical);
+            break;
+        }
+    }
+    if (win_mask && n_rows) {
+        if (mask_mem == CRDT_MEM_HOST)
+            HIPCHK(hipMemcpyAsync(win_mask, wm, n_rows, hipMemcpyDeviceToHost, dst->stream));
+        HIPCHK(hipStreamSynchronize(dst->stream));
+    }
+    return st;
+}
+
+int crdt_fanin_tables(crdt_ctx* dst, crdt_ctx* const* srcs, const int64_t* since_lt, uint32_t n_src,
+                      uint64_t n_rows, int64_t wall, uint8_t* win_mask, int32_t mask_mem, crdt_result* out) {
+    if (!dst || !srcs || !since_lt || !out || n_src == 0 || n_src > CRDT_FANIN_MAX) return CRDT_E_INVALID;
+    for (uint32_t j = 0; j < n_src; ++j)
+        if (!srcs[j]) return CRDT_E_INVALID;                  // (every null check before a ctx is read)
+    bool self = false;
+    for (uint32_t j = 0; j < n_src; ++j) {
+        if (!tm_args_ok(dst, srcs[j], win_mask != nullptr, mask_mem) || n_rows > srcs[j]->cap) return CRDT_E_INVALID;
+        self |= srcs[j] == dst;
+    }
+    if (n_src == 1) return crdt_merge_table(dst, srcs[0], n_rows, since_lt[0], wall, win_mask, mask_mem, out);
+    HIPCHK(hipSetDevice(dst->device));
+    if (dst->env_dynamic) read_env_knobs(dst);
+    // the composition: switched to, dst among its sources, or dst pinned to the sorted path (as crdt_merge_table)
+    if (!dst->table_merge || self || dst->merge_path == CRDT_PATH_SORTED)
+        return fanin_tables_composed(dst, srcs, since_lt, n_src, n_rows, wall, win_mask, mask_mem, out);
+    uint64_t rows[kFanMax], covered = 0;
+    for (uint32_t j = 0; j < n_src; ++j) {
+        HIPCHK(hipStreamSynchronize(srcs[j]->stream));        // the sources' rows are final before dst's stream reads them
+        rows[j] = ex_rows(srcs[j], n_rows, since_lt[j]);
+        covered = std::max(covered, rows[j]);
+    }
+    const unsigned nb = grid_for(covered, kTmTile);
+    uint8_t* rf;
+    int st;
+    if ((st = tm_stage_flags(dst, win_mask, mask_mem, n_rows, &rf))) return st;
+    if ((st = tm_begin(dst, nb, (int)n_src))) return st;
+    // pass 1, once per source: its clock words, and its counts and bits over all nb tiles (zeros past its own
+    // rows).  The candidate bit is taken against C_0: canonicals never decrease, so a row that can raise in
+    // merge j's recv() lies above C_{j-1} >= C_0, and no bit means that no recv() of the sequence raises.
+    const int64_t c0 = dst->canonical;
+    for (uint32_t j = 0; j < n_src && nb; ++j) {
+        uint32_t* sel = dst->t_sel.p + (size_t)j * nb;
+        if (rows[j] == 0) {                                   // (its mask words are never read: the count is zero)
+            HIPCHK(hipMemsetAsync(sel, 0, (size_t)nb * sizeof(uint32_t), dst->stream));
+            continue;
+        }
+        k_tm_clock<<<std::min(nb, kTmClockGrid), kTmThreads, 0, dst->stream>>>(
+            srcs[j]->table, rows[j], since_lt[j], nb, c0, wall, dst->local_rank, sel,
+            dst->t_mask.p + (size_t)j * nb * kTmMaskWords, dst->t_words.p + (size_t)j * kTmWords);
+        HIPCHK(hipGetLastError());
+    }
+    unsigned long long w[kFanMax * kTmWords] = {};
+    if ((st = tm_read_words(dst, w, (int)n_src))) return st;
+    // the chain R_j = max(C_{j-1}, max lt of selection j), C_j = Hlc.send(R_j).  A row that may raise, a
+    // selected id outside dst, or a send() that raises (the sequence ends there): nothing is written yet, the
+    // composition gives the exact stop point, exception details and error
+    FanArgs fa{};
+    crdt_result res[kFanMax];
+    int64_t c = c0;
+    bool composed = false, has = false;
+    for (uint32_t j = 0; j < n_src; ++j) {
+        const unsigned long long* wj = w + j * kTmWords;
+        composed |= wj[2] || (wj[3] && wj[1] > dst->cap);
+        has |= wj[3] != 0;
+        fa.src[j] = srcs[j]->table;
+        fa.rows[j] = rows[j];
+        fa.stamp[j] = tm_recv_canonical(c, wj);
+        res[j] = cleared_result(c);
+        res[j].n_stored = 1;
+        hlc_send(fa.stamp[j], wall).into(res[j]);
+        composed |= res[j].status != CRDT_OK;
+        c = res[j].canonical_lt;
+    }
+    if (composed) return fanin_tables_composed(dst, srcs, since_lt, n_src, n_rows, wall, win_mask, mask_mem, out);
+    ev_record(dst, kEvClock);
+    // pass 2: dst's row once, the sources folded over it in call order, the last winner stored
+    HIPALLOC(dst->t_fcounts.ensure(kFanCounts));
+    HIPCHK(hipMemsetAsync(dst->t_fcounts.p, 0, kFanCounts * sizeof(unsigned long long), dst->stream));
+    if ((st = tm_zero_uncovered(dst, rf, has ? covered : 0, n_rows))) return st;
+    tm_apply_begin(dst, has);
+    if (has) {
+        k_fan_apply<<<nb, kTmThreads, 0, dst->stream>>>(fa, n_src, dst->table, covered, nb, dst->t_sel.p,
+                                                        dst->t_mask.p, dst->t_fcounts.p, rf);
+        HIPCHK(hipGetLastError());
+    }
+    tm_apply_end(dst, has);
+    if ((st = tm_flags_to_host(dst, win_mask, rf, mask_mem, n_rows))) return st;
+    std::vector<unsigned long long> counts(kFanCounts);
+    HIPCHK(hipMemcpyAsync(counts.data(), dst->t_fcounts.p, kFanCounts * sizeof(unsigned long long),
+                          hipMemcpyDeviceToHost, dst->stream));
+    HIPCHK(hipStreamSynchronize(dst->stream));
+    // per source: its counts from the call's own words (no Misc slots: tm_finish sums none), and on dst the
+    // mark (it rises to the largest selected id of all), the canonical C_j and what crdt_last_plan reports
+    for (uint32_t j = 0; j < n_src; ++j) {
+        const unsigned long long* cj = counts.data() + 2 * j * kCounterSlots;
+        for (int s = 0; s < kCounterSlots; ++s) {
+            res[j].n_present += cj[s];
+            res[j].n_won += cj[kCounterSlots + s];
+        }
+        tm_finish(dst, &res[j], dst->h_misc, 0, 0, w + j * kTmWords, false);
+        out[j] = res[j];
+    }
+    dst->last_fanin = true;
+    collect_timing(dst);
+    return CRDT_OK;
+}
+
 int crdt_set_rank_bound(crdt_ctx* c, uint32_t bound) {
     if (!c) return CRDT_E_INVALID;
     c->rank_bound = bound;
@@ -4421,7 +4564,10 @@ int crdt_last_path(const crdt_ctx* c, int* path) {
 int crdt_last_plan(const crdt_ctx* c, uint32_t* flags) {
     if (!c || !flags) return CRDT_E_INVALID;
     uint32_t f = 0;
-    if (c->last_table) { *flags = CRDT_PLAN_TABLE | (c->last_sync ? CRDT_PLAN_SYNC : 0u); return CRDT_OK; }
+    if (c->last_table) {
+        *flags = CRDT_PLAN_TABLE | (c->last_sync ? CRDT_PLAN_SYNC : 0u) | (c->last_fanin ? CRDT_PLAN_FANIN : 0u);
+        return CRDT_OK;
+    }
     if (c->last_sorted) {
         f |= CRDT_PLAN_SORTED;
         if (c->last_packed) f |= CRDT_PLAN_PACKED;

@@ -1,6 +1,7 @@
 // table_merge.inc — crdt_merge_table: dst.merge(src.recordMap(modifiedSince)) between two tables of one
-// device and one id space, without an export (crdt.dart:77-94 on the changeset of crdt.dart:157-160), and
-// crdt_sync_tables, the two-way exchange on one read of both tables (further down).
+// device and one id space, without an export (crdt.dart:77-94 on the changeset of crdt.dart:157-160),
+// crdt_sync_tables, the two-way exchange on one read of both tables, and crdt_fanin_tables, up to eight
+// sources merged into one table on one read of it (both further down).
 // Included from crdt_merge.hip inside its anonymous namespace, beside the export kernels.
 //
 // Key k lives in row k of BOTH tables, so the merge is an element-wise pass over two aligned arrays:
@@ -122,9 +123,11 @@ struct TmClock {
     }
 };
 
-// The workgroup's sums of these per-thread counts onto present[slot] / won[slot]: one pair of atomics.
+// The workgroup's sums of these per-thread counts onto *present / *won (Misc's striped present[slot] /
+// won[slot] in the second form): one pair of atomics.
 // Every thread calls it (it has a barrier); s is its own.
-__device__ inline void tm_add_counts(int npres, int nwon, int (&s)[2][4], Misc* __restrict__ misc, int slot) {
+__device__ inline void tm_add_counts(int npres, int nwon, int (&s)[2][4], unsigned long long* __restrict__ present,
+                                     unsigned long long* __restrict__ won) {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
@@ -136,8 +139,11 @@ __device__ inline void tm_add_counts(int npres, int nwon, int (&s)[2][4], Misc* 
     if (threadIdx.x != 0) return;
     npres = s[0][0] + s[0][1] + s[0][2] + s[0][3];
     nwon = s[1][0] + s[1][1] + s[1][2] + s[1][3];
-    if (npres) atomicAdd(&misc->present[slot], (unsigned long long)npres);
-    if (nwon) atomicAdd(&misc->won[slot], (unsigned long long)nwon);
+    if (npres) atomicAdd(present, (unsigned long long)npres);
+    if (nwon) atomicAdd(won, (unsigned long long)nwon);
+}
+__device__ inline void tm_add_counts(int npres, int nwon, int (&s)[2][4], Misc* __restrict__ misc, int slot) {
+    tm_add_counts(npres, nwon, s, &misc->present[slot], &misc->won[slot]);
 }
 
 __global__ __launch_bounds__(kTmThreads) void k_tm_clock(Table src, uint64_t n, int64_t since, uint32_t nb,
@@ -386,4 +392,136 @@ __global__ __launch_bounds__(kTmThreads) void k_sy_apply(Table ta, Table tb, uin
     const int slot = blockIdx.x & (kCounterSlots / 2 - 1);
     tm_add_counts(np1, nw1, s_pw[0], misc, slot);
     tm_add_counts(np2, nw2, s_pw[1], misc, kCounterSlots / 2 + slot);
+}
+
+// ---- crdt_fanin_tables: the hub, for j < n_src: dst.merge(srcs[j].recordMap(since_j)), n_src <= kFanMax, on
+// ONE read of dst's row (DESIGN §6f).  The win decision reads no canonical clock and the call writes no
+// source, so every source's selection and clock words are known before anything is stored: k_tm_clock runs
+// as it is once per source (source j's counts in sel[j * nb ..], its bits in mask[j * nb * kTmMaskWords ..],
+// its words in words[4 j ..], every launch over all nb tiles with the source's own row bound and dst's
+// canonical at entry for the candidate bit), the host chains R_j = max(C_{j-1}, max lt of selection j),
+// C_j = Hlc.send(R_j), and
+//   k_fan_apply one workgroup per tile; a tile no source selected writes its zero mask bytes and returns.
+//               Else a thread takes its selection bits of every source that selected in the tile (eight bits
+//               a source, kept in one 64-bit word: the loop below issues no dependent mask load), loads dst's
+//               decision half for its rows that ANY source selected (the others read row 0) and keeps the
+//               running row {lt, rank, mod, val} in registers.  The sources follow
+//               in call order, a runtime loop with one source's loads in flight at a time (a source that
+//               selected nothing in the tile is skipped): its selected rows' decision half and val, the plain
+//               rule on the running row (wins iff that is invisible or hlc_gt(src, running); the visibility
+//               of a row stored earlier in the call is the sign of its stamp R_i, as the next
+//               crdt_merge_table would read it), and a winner replaces the running {lt, rank, val}, takes
+//               mod = R_j and sets bit j of the row's outcome byte.  After the loop a row whose byte is
+//               non-zero is stored ONCE; the byte goes to win_mask[row] (optional) in any case.
+//               n_present / n_won per source, in words of the call's own (counts[]: source j's present in
+//               [128 j, 128 j + 64), its won in the 64 after them, striped by tile as Misc's are: eight slots
+//               a source of Misc's 64 would put 8192 tiles' atomics of a 2^27-row call on one address).
+constexpr int kFanMax = 8;                       // CRDT_FANIN_MAX: one outcome bit per source in a byte
+constexpr int kFanCounts = kFanMax * 2 * kCounterSlots;   // words of counts[]
+static_assert(kFanMax == CRDT_FANIN_MAX, "the header's bound");
+static_assert(kFanMax <= 8, "one mask bit per source");
+static_assert(kTmItems * 8 <= 64, "a thread's outcome bytes travel in one 64-bit word");
+
+struct FanArgs {                                 // by value: the sources' tables, row bounds and stamps R_j
+    Table src[kFanMax];
+    uint64_t rows[kFanMax];
+    int64_t stamp[kFanMax];
+};
+
+__global__ __launch_bounds__(kTmThreads) void k_fan_apply(FanArgs a, uint32_t n_src, Table dst, uint64_t n,
+                                                          uint32_t nb, const uint32_t* __restrict__ sel,
+                                                          const unsigned long long* __restrict__ mask,
+                                                          unsigned long long* __restrict__ counts,
+                                                          uint8_t* __restrict__ flags)
+{
+    __shared__ int s_pw[kFanMax][2][4];
+    const uint32_t tile = blockIdx.x;
+    const uint64_t base = (uint64_t)tile * kTmTile;
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // (wave-uniform: the mask words load as scalars)
+    // the sources that selected in this tile (the counts load together), then this thread's selection bits of
+    // each of them, kept for the loop below: bit 8 j + q = source j selected row q
+    uint32_t active = 0;
+#pragma unroll
+    for (int j = 0; j < kFanMax; ++j) {
+        const uint32_t cnt = sel[(uint64_t)((uint32_t)j < n_src ? j : 0) * nb + tile];   // (always inside sel[])
+        active |= (uint32_t)((uint32_t)j < n_src && cnt != 0) << j;
+    }
+    if (active == 0) {                           // the whole workgroup: no source selected in this tile
+        tm_zero_flags(flags, base, n);
+        return;
+    }
+    unsigned long long bits = 0;
+    for (uint32_t j = 0; j < n_src; ++j) {
+        if (!((active >> j) & 1u)) continue;     // (its words may never have been written)
+        const unsigned long long* m = mask + ((uint64_t)j * nb + tile) * kTmMaskWords;
+        uint32_t b = 0;
+#pragma unroll
+        for (int q = 0; q < kTmItems; ++q) b |= (uint32_t)((m[q * 4 + w] >> lane) & 1ull) << q;
+        bits |= (unsigned long long)b << (8 * j);
+    }
+    uint32_t any = (uint32_t)bits | (uint32_t)(bits >> 32);   // the rows any source selected
+    any |= any >> 16;
+    any |= any >> 8;
+    uint4 r[kTmItems];                           // the running row: {lt, rank, mod_hi}
+    uint32_t rl[kTmItems], rv[kTmItems];         // its mod_lo and val (of a winner; a row that never wins is not stored)
+#pragma unroll
+    for (int q = 0; q < kTmItems; ++q) {
+        // (the host sent a call with a selected id >= dst's capacity elsewhere; an unselected lane reads row 0)
+        r[q] = load_hot(dst, (any >> q) & 1u ? tm_row(base, q) : 0);
+        rl[q] = rv[q] = 0;
+    }
+    unsigned long long won = 0;                  // byte q: the outcome byte of row q
+#pragma unroll 1
+    for (uint32_t j = 0; j < n_src; ++j) {
+        if (!((active >> j) & 1u)) continue;     // (the whole workgroup)
+        const Table src = a.src[j];
+        const uint64_t nj = a.rows[j];
+        const uint32_t mine = (uint32_t)(bits >> (8 * j));
+        uint4 h[kTmItems];
+        uint32_t v[kTmItems];
+        uint32_t keep = 0;
+#pragma unroll
+        for (int q = 0; q < kTmItems; ++q) {
+            const uint64_t i = tm_row(base, q);
+            const bool k = ((mine >> q) & 1u) && i < nj;       // (the clock pass set bits of rows < nj only)
+            keep |= (uint32_t)k << q;
+            const uint64_t ic = k ? i : 0;
+            h[q] = load_hot(src, ic);
+            v[q] = *reinterpret_cast<const uint32_t*>(row_ptr(src, ic) + 20);
+        }
+        const uint32_t st_hi = (uint32_t)((uint64_t)a.stamp[j] >> 32), st_lo = (uint32_t)a.stamp[j];
+        int npres = 0, nwon = 0;
+#pragma unroll
+        for (int q = 0; q < kTmItems; ++q) {
+            const bool k = (keep >> q) & 1u;
+            const bool present = (int32_t)r[q].w >= 0;
+            const bool win = k && (!present || hlc_gt(h[q], r[q]));
+            npres += k && present;
+            nwon += win;
+            if (win) {
+                r[q] = make_uint4(h[q].x, h[q].y, h[q].z, st_hi);
+                rl[q] = st_lo;
+                rv[q] = v[q];
+            }
+            won |= (unsigned long long)win << (q * 8 + j);
+        }
+        unsigned long long* c = counts + (2 * j * kCounterSlots + (tile & (kCounterSlots - 1)));
+        tm_add_counts(npres, nwon, s_pw[j], c, c + kCounterSlots);
+    }
+#pragma unroll
+    for (int q = 0; q < kTmItems; ++q) {
+        const uint64_t i = tm_row(base, q);
+        const uint32_t b = (uint32_t)(won >> (q * 8)) & 0xFFu;
+        if (b) store_hc(dst, i, r[q], make_uint2(rl[q], rv[q]));
+        if (flags && i < n) flags[i] = (uint8_t)b;
+    }
+}
+
+// The composition's mask: step j's row flags into bit j.
+__global__ __launch_bounds__(256) void k_fan_or_flags(const uint8_t* __restrict__ step, uint64_t n, uint32_t j,
+                                                      uint8_t* __restrict__ win_mask)
+{
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
+        if (step[i]) win_mask[i] |= (uint8_t)(1u << j);
 }

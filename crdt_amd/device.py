@@ -314,6 +314,29 @@ class DeviceTable:
             arr_b = arr_b[:n_rows]
         return (res_a.as_dict(), arr_a), (res_b.as_dict(), arr_b)
 
+    def merge_tables(self, srcs, n_rows: int, sinces, wall: int, win_mask=False):
+        """The hub: ``for s, since in zip(srcs, sinces): self.merge(s.recordMap(modifiedSince: since))`` for up
+        to ``_capi.FANIN_MAX`` source tables, decided on one read of this table (``crdt_fanin_tables``); exactly
+        what the ``merge_table`` calls leave, the sequence ending at the first that raises.  Returns (list of
+        result dicts, one per source; mask or None): ``mask[i]`` has bit j set where merge j stored row i.
+        ``win_mask``: as ``merge_table``'s ``row_flags``."""
+        srcs, sinces = list(srcs), [int(s) for s in sinces]
+        if len(sinces) != len(srcs):
+            raise ValueError(f"merge_tables: {len(srcs)} sources but {len(sinces)} sinces")
+        for s in srcs:
+            if s.device != self.device:
+                raise ValueError(f"merge_tables: a source table is on device {s.device}, this one on {self.device}")
+        n_rows, n_src = int(n_rows), len(srcs)
+        mask_arr, mptr, mem = self._row_flags_arg(win_mask, n_rows)
+        ctxs = (ctypes.c_void_p * max(n_src, 1))(*(s._ctx.value for s in srcs))
+        since_arr = (ctypes.c_int64 * max(n_src, 1))(*sinces)
+        res = (CrdtResult * max(n_src, 1))()
+        st = self._lib.crdt_fanin_tables(self._ctx, ctxs, since_arr, n_src, n_rows, int(wall), mptr, mem, res)
+        self._check(st, "crdt_fanin_tables")
+        if win_mask is True:
+            mask_arr = mask_arr[:n_rows]
+        return [res[j].as_dict() for j in range(n_src)], mask_arr
+
     def clear_rows(self, first: int, count: int):
         self._check(self._lib.crdt_clear_rows(self._ctx, first, count), "crdt_clear_rows")
 
@@ -469,7 +492,7 @@ class DeviceTable:
                   "flagged": 1024, "ordered": 2048,
                   "combined": 4096, "route_l1": 8192, "route_tuned": 16384, "rl1_head": 262144,
                   "compact": 524288, "hot_direct": 1048576, "table": 2097152,
-                  "sync": 4194304}
+                  "sync": 4194304, "fanin": 8388608}
 
     def last_plan(self) -> dict:
         """crdt_last_plan: how the last merge ran ({'sorted': bool, 'packed': ..., ...})."""

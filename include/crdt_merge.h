@@ -295,6 +295,48 @@ int crdt_sync_tables(crdt_ctx* a, crdt_ctx* b, uint64_t n_rows, int64_t since_a,
                      int64_t wall_millis, uint8_t* flags_a, uint8_t* flags_b, int32_t flags_mem,
                      crdt_result* out_a, crdt_result* out_b);
 
+/* The hub: for j in 0 .. n_src-1: dst.merge(srcs[j].recordMap(modifiedSince: since_lt[j])), 1 <= n_src <=
+ * CRDT_FANIN_MAX ctxs on the SAME device sharing one key / node / value interning.  For every input it leaves
+ * exactly what
+ *     for (j = 0; j < n_src; ++j) {
+ *         s_j = crdt_merge_table(dst, srcs[j], n_rows, since_lt[j], wall_millis, flags_j, mask_mem, &out[j]);
+ *         if (s_j != 0) break;
+ *     }
+ * leaves: dst's rows and canonical, every field of every out[j], the return value (the first non-zero s_j,
+ * else 0) and the mask.  win_mask (optional, memory of kind mask_mem): [n_rows] bytes indexed by ROW id, every
+ * entry written: win_mask[i] = OR_j (flags_j[i] << j), bit j set where merge j stored row i (the watch()
+ * events of the n_src merges; a row can be stored more than once in one call).  After a stop at step j the
+ * steps before j stay merged (a negative s_j does not undo them), every out[k], k > j, is zero except
+ * exc_index = UINT64_MAX and canonical_lt = dst's canonical at the stop, and no bit k > j is set.  An empty
+ * selection is still one merge() call: its closing Hlc.send advances dst's canonical.  The sources are
+ * read-only (rows, canonical, plan and export view untouched, and dst's export view too); a source may appear
+ * more than once.  n_src == 1 runs crdt_merge_table and reports its plan.
+ * The win decision (crdt.dart:83-84) reads no canonical clock and no source is written, so the whole call is
+ * decided on ONE read of dst's row: crdt_merge_table's clock pass once per source (its tile counts, one
+ * selection bit per row, four words; the candidate bit against dst's canonical at entry, C_0: canonicals
+ * never decrease, so no candidate against C_0 means that no recv() of the sequence raises), one read-back of
+ * 4 * n_src words, the host's chain R_j = max(C_{j-1}, max lt of selection j), C_j = Hlc.send(R_j), and one
+ * apply pass that skips the tiles no source selected, loads dst's row once, folds the sources' selected rows
+ * over it in registers in call order (the plain rule; a row stored by an earlier step is visible iff its
+ * stamp R_i is non-negative) and stores the last winner with mod = its step's R.  Scratch, on dst: 4 * n_src
+ * words, n_src counts per tile and n_src bits per row (134 MB for 8 sources of 2^27 rows); nothing grows
+ * with the selection.
+ * The call runs the composition above itself, nothing written by then, whenever a selected row is a candidate
+ * against C_0 (lt above C_0 with dst's node id, or over 60000 ms ahead of wall_millis), a selected id is >=
+ * dst's capacity, any Hlc.send of the chain raises, a srcs[j] is dst, dst is pinned to CRDT_PATH_SORTED, or
+ * dst was created under CRDT_TABLE_MERGE=0.
+ * CRDT_E_INVALID, nothing touched: a null dst, srcs, since_lt, out or srcs[j] (checked before any ctx is
+ * read), n_src == 0 or > CRDT_FANIN_MAX, n_rows above any source's capacity, a ctx on another device, a ctx
+ * joined to a communicator, a bad mask_mem with a mask pointer.  No ctx involved may be in another call; the
+ * work runs on dst's stream after every source's is drained, and the call is synchronous.  After the fused
+ * form crdt_last_plan(dst) is CRDT_PLAN_TABLE | CRDT_PLAN_FANIN and crdt_last_path(dst) CRDT_PATH_GATHER
+ * (after a fallback: what the composition's last call reports); crdt_timing on dst gets scan_ms (the clock
+ * passes), apply_ms (the apply pass) and total_ms. */
+#define CRDT_FANIN_MAX 8
+int crdt_fanin_tables(crdt_ctx* dst, crdt_ctx* const* srcs, const int64_t* since_lt, uint32_t n_src,
+                      uint64_t n_rows, int64_t wall_millis, uint8_t* win_mask, int32_t mask_mem,
+                      crdt_result* out /* [n_src] */);
+
 /* ---- key-sharded multi-GPU (north star config 4) -------------
  * n_ranks ctxs — one per GPU, normally one process per GPU — form ONE replica whose
  * keys are sharded: rank d owns key k iff k % n_ranks == d and stores it at slot
@@ -448,8 +490,10 @@ enum crdt_plan_flags {
                                     final bucket; they skipped level 2 (sorted_path.inc, HotL1) */
     CRDT_PLAN_TABLE = 2097152,    /* the last merge on this ctx was a crdt_merge_table that ran the fused table
                                     form (table_merge.inc); set alone */
-    CRDT_PLAN_SYNC = 4194304      /* ... or, with CRDT_PLAN_TABLE, one side of a crdt_sync_tables that ran its
+    CRDT_PLAN_SYNC = 4194304,     /* ... or, with CRDT_PLAN_TABLE, one side of a crdt_sync_tables that ran its
                                     fused two-way form (set on both ctxs) */
+    CRDT_PLAN_FANIN = 8388608     /* ... or, with CRDT_PLAN_TABLE, the destination of a crdt_fanin_tables that ran
+                                    its fused form */
 };
 int crdt_last_plan(const crdt_ctx* ctx, uint32_t* flags);
 
