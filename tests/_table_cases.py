@@ -99,3 +99,63 @@ def decisions(src: dict, dst: dict, n_rows: int, since: int) -> dict:
         "older_wins_invisible": int(np.count_nonzero(sel & ~vis & ~newer)),
         "tombstone_wins": int(np.count_nonzero(sel & (s["val"] == NULL) & (~vis | newer))),
     }
+
+
+# ------------------------------------------------------------------ the contracts on the C restatement
+# The compositions that crdt_merge_table, crdt_sync_tables, crdt_fanin_tables and merge_from are held to,
+# on OracleTable objects (oracle/oracle_c.py; nothing here imports the library).  Every value a GPU test
+# compares comes from these.
+RESULT_FIELDS = ("status", "n_stored", "exc_changeset", "exc_index", "canonical_lt", "drift_ms", "counter",
+                 "n_present", "n_won")
+U64_MAX = (1 << 64) - 1
+CLEARED = {"status": 0, "n_stored": 0, "exc_changeset": 0, "exc_index": U64_MAX, "drift_ms": 0, "counter": 0,
+           "n_present": 0, "n_won": 0}
+
+
+def oracle_merge_from(dst, src, n_rows: int, since: int, wall: int):
+    """dst.merge(src.recordMap(modifiedSince)); returns (result dict, flags by RECORD, records)."""
+    ids = src.modified_since(n_rows, since)
+    rows = src.rows[ids]
+    res, flags = dst.merge(ids, rows["lt"].copy(), rows["rank"].copy(), rows["val"].copy(),
+                           np.array([0, len(ids)], np.uint64), wall)
+    return res.as_dict(), flags, len(ids)
+
+
+def oracle_merge_table(odst, osrc, n_rows: int, since: int, wall: int):
+    """The composition on the oracle; returns (result dict, flags by ROW id, selected ids)."""
+    ids = osrc.modified_since(n_rows, since)
+    rows = osrc.rows[ids]
+    res, flags = odst.merge(ids, rows["lt"].copy(), rows["rank"].copy(), rows["val"].copy(),
+                            np.array([0, len(ids)], np.uint64), wall)
+    row_flags = np.zeros(n_rows, np.uint8)
+    row_flags[ids[flags != 0]] = 1
+    return res.as_dict(), row_flags, ids
+
+
+def oracle_sync(oa, ob, n_rows, since_a, since_b, wall):
+    """crdt_sync_tables' contract on the oracle: ((result a, flags a), (result b, flags b))."""
+    res_a, fl_a, _ = oracle_merge_table(oa, ob, n_rows, since_b, wall)
+    if res_a["status"] == 0:
+        res_b, fl_b, _ = oracle_merge_table(ob, oa, n_rows, since_a, wall)
+    else:
+        res_b = {f: 0 for f in RESULT_FIELDS}
+        res_b["exc_index"] = U64_MAX
+        res_b["canonical_lt"] = ob.canonical
+        fl_b = np.zeros(n_rows, np.uint8)
+    return (res_a, fl_a), (res_b, fl_b)
+
+
+def oracle_fanin(odst, osrcs, n_rows, sinces, wall):
+    """crdt_fanin_tables' contract on the oracle: (results, mask, index of the step that stopped the
+    sequence or None)."""
+    results, mask, stop = [], np.zeros(n_rows, np.uint8), None
+    for j, (osrc, since) in enumerate(zip(osrcs, sinces)):
+        if stop is not None:
+            results.append(dict(CLEARED, canonical_lt=odst.canonical))
+            continue
+        res, flags, _ = oracle_merge_table(odst, osrc, n_rows, since, wall)
+        results.append(res)
+        mask |= (flags << j).astype(np.uint8)
+        if res["status"] != 0:
+            stop = j
+    return results, mask, stop

@@ -10,6 +10,7 @@ from crdt_amd import CrdtJson, CrdtNativeError, DeviceTable, Hlc, MapCrdt, Recor
 from crdt_amd.crdt import Crdt
 from oracle.oracle_c import OracleTable, new_table
 from tests._cases import ABSENT_MOD, NULL, WALL, make_case
+from tests._table_cases import oracle_merge_from as _oracle_merge_from   # (the contract on the oracle)
 
 pytestmark = pytest.mark.gpu
 
@@ -212,14 +213,6 @@ def _diverge(t, o, case):
     ores, _ = o.merge(*batch)
     assert res["status"] == ores.status == 0
     assert res["canonical_lt"] == o.canonical
-
-
-def _oracle_merge_from(dst: OracleTable, src: OracleTable, n_rows: int, since: int, wall: int):
-    ids = src.modified_since(n_rows, since)
-    rows = src.rows[ids]
-    res, flags = dst.merge(ids, rows["lt"].copy(), rows["rank"].copy(), rows["val"].copy(),
-                           np.array([0, len(ids)], np.uint64), wall)
-    return res.as_dict(), flags, len(ids)
 
 
 def _check_rows(t: DeviceTable, o: OracleTable, tag):

@@ -24,8 +24,7 @@ RESULT_FIELDS = gt.RESULT_FIELDS
 COLS = fc.COLS
 DRIFT_LT = gt.DRIFT_LT
 DUP_LT = (MW + 10) << 16                 # above every running canonical of a call at MW, within the drift bound
-CLEARED = {"status": 0, "n_stored": 0, "exc_changeset": 0, "exc_index": U64_MAX, "drift_ms": 0, "counter": 0,
-           "n_present": 0, "n_won": 0}
+CLEARED = tc.CLEARED
 
 
 def close(*tables):
@@ -43,19 +42,7 @@ def load_dst(rows, cap, stride=24, canonical=None):
     return gt.load(rows, cap, stride, local_rank=fc.DST_RANK, canonical=sc.canon0() if canonical is None else canonical)
 
 
-def oracle_fanin(odst, osrcs, n_rows, sinces, wall):
-    """The contract on the oracle: (results, mask, index of the step that stopped the sequence or None)."""
-    results, mask, stop = [], np.zeros(n_rows, np.uint8), None
-    for j, (osrc, since) in enumerate(zip(osrcs, sinces)):
-        if stop is not None:
-            results.append(dict(CLEARED, canonical_lt=odst.canonical))
-            continue
-        res, flags, _ = gt.oracle_merge_table(odst, osrc, n_rows, since, wall)
-        results.append(res)
-        mask |= (flags << j).astype(np.uint8)
-        if res["status"] != 0:
-            stop = j
-    return results, mask, stop
+oracle_fanin = tc.oracle_fanin                        # (the contract on the oracle: tests/_table_cases.py)
 
 
 def check_fanin(dst, odst, srcs, osrcs, n_rows, sinces, wall, tag, fused="model", win_mask=True):

@@ -36,17 +36,7 @@ def close(*tables):
         t.close()
 
 
-def oracle_sync(oa, ob, n_rows, since_a, since_b, wall):
-    """The contract on the oracle: ((result a, flags a), (result b, flags b))."""
-    res_a, fl_a, _ = gt.oracle_merge_table(oa, ob, n_rows, since_b, wall)
-    if res_a["status"] == 0:
-        res_b, fl_b, _ = gt.oracle_merge_table(ob, oa, n_rows, since_a, wall)
-    else:
-        res_b = {f: 0 for f in RESULT_FIELDS}
-        res_b["exc_index"] = U64_MAX
-        res_b["canonical_lt"] = ob.canonical
-        fl_b = np.zeros(n_rows, np.uint8)
-    return (res_a, fl_a), (res_b, fl_b)
+oracle_sync = tc.oracle_sync                          # (the contract on the oracle: tests/_table_cases.py)
 
 
 def check_sync(a, oa, b, ob, n_rows, since_a, since_b, wall, tag, fused="model", row_flags=True):

@@ -50,15 +50,7 @@ def assert_rows(t: DeviceTable, o: OracleTable, tag):
     assert t.canonical == o.canonical, tag
 
 
-def oracle_merge_table(odst: OracleTable, osrc: OracleTable, n_rows: int, since: int, wall: int):
-    """The composition on the oracle; returns (result dict, flags by ROW id, selected ids)."""
-    ids = osrc.modified_since(n_rows, since)
-    rows = osrc.rows[ids]
-    res, flags = odst.merge(ids, rows["lt"].copy(), rows["rank"].copy(), rows["val"].copy(),
-                            np.array([0, len(ids)], np.uint64), wall)
-    row_flags = np.zeros(n_rows, np.uint8)
-    row_flags[ids[flags != 0]] = 1
-    return res.as_dict(), row_flags, ids
+oracle_merge_table = tc.oracle_merge_table         # (the contract on the oracle: tests/_table_cases.py)
 
 
 def check(dst, odst, src, osrc, n_rows, since, wall, tag, table=True, row_flags=True):
