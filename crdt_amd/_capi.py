@@ -69,6 +69,7 @@ EXPORT_COUNT_GRID = 2048                   # workgroups of its count pass, strid
 TABLE_TILE = 2048                          # rows per workgroup of crdt_merge_table's two passes (table_merge.inc kTmTile)
 TABLE_CLOCK_GRID = 2048                    # workgroups of its clock pass, striding over the tiles (kTmClockGrid)
 FANIN_MAX = 8                              # sources of one crdt_fanin_tables (include/crdt_merge.h CRDT_FANIN_MAX)
+FANOUT_MAX = 8                             # destinations of one crdt_fanout_tables (CRDT_FANOUT_MAX)
 SYNC_CLOCK_GRID = 2048                     # workgroups of crdt_sync_tables' clock pass (table_merge.inc kSyClockGrid)
 
 # crdt_comm_ops callbacks (include/crdt_merge.h)
@@ -125,6 +126,7 @@ SIGNATURES = {
     "crdt_merge_table": (_INT, [_P, _P, _U64, _I64, _I64, _P, _I32, _P]),
     "crdt_sync_tables": (_INT, [_P, _P, _U64, _I64, _I64, _I64, _P, _P, _I32, _P, _P]),
     "crdt_fanin_tables": (_INT, [_P, _P, _P, _U32, _U64, _I64, _P, _I32, _P]),
+    "crdt_fanout_tables": (_INT, [_P, _P, _P, _U32, _U64, _I64, _P, _I32, _P]),
     "crdt_comm_unique_id": (_INT, [_P]),
     "crdt_comm_init_rccl": (_INT, [_P, _U32, _U32, _P]),
     "crdt_comm_init_ops": (_INT, [_P, _U32, _U32, _P]),

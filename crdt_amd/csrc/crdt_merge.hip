@@ -1863,6 +1863,7 @@ struct crdt_ctx {
     bool last_table = false;           // the last merge on this ctx ran the fused table form
     bool last_sync = false;            // ... as one side of a fused crdt_sync_tables
     bool last_fanin = false;           // ... as the destination of a fused crdt_fanin_tables
+    bool last_fanout = false;          // ... as a destination of a fused crdt_fanout_tables
     DBuf<long long> d_word;
     DBuf<unsigned long long> d_ibase;
     // per-call plan (set by scan, used by later phases)
@@ -4045,6 +4046,7 @@ int crdt_merge(crdt_ctx* c, const crdt_batch* batch, int64_t wall, uint8_t* win_
     c->last_table = false;
     c->last_sync = false;
     c->last_fanin = false;
+    c->last_fanout = false;
     // rows >= hw_read are read as the fill by this merge; afterwards hw moves to hw_next (the
     // capacity unless finish_apply learned the batch's key bound) on every return path
     c->hw_read = (c->form_off & kFormNoHw) ? c->cap : c->hw;
@@ -4206,6 +4208,7 @@ static void tm_finish(crdt_ctx* c, crdt_result* res, const Misc* m, int first, i
     c->last_table = true;
     c->last_sync = sync;
     c->last_fanin = false;
+    c->last_fanout = false;
     c->last_sorted = false;
 }
 
@@ -4537,6 +4540,143 @@ int crdt_fanin_tables(crdt_ctx* dst, crdt_ctx* const* srcs, const int64_t* since
     return CRDT_OK;
 }
 
+// ---- crdt_fanout_tables: for j < n_dst: dsts[j].merge(src.recordMap(since_j)) (table_merge.inc)
+// The composition itself: the crdt_merge_table calls of the contract, in call order, until one returns
+// non-zero; each step's row flags go into bit j of the mask (staged on dsts[0], as fanin_tables_composed
+// stages on dst).  Exact by construction; the fused form falls back to it, with nothing written yet.
+static int fanout_tables_composed(crdt_ctx* src, crdt_ctx* const* dsts, const int64_t* since, uint32_t n_dst,
+                                  uint64_t n_rows, int64_t wall, uint8_t* win_mask, int32_t mask_mem,
+                                  crdt_result* out) {
+    crdt_ctx* d0 = dsts[0];
+    uint8_t* step = nullptr;
+    uint8_t* wm = win_mask;
+    if (win_mask) {
+        HIPALLOC(d0->t_fstep.ensure(n_rows ? n_rows : 1));
+        step = d0->t_fstep.p;
+        if (mask_mem == CRDT_MEM_HOST) {
+            HIPALLOC(d0->t_fmask.ensure(n_rows ? n_rows : 1));
+            wm = d0->t_fmask.p;
+        }
+        if (n_rows) HIPCHK(hipMemsetAsync(wm, 0, n_rows, d0->stream));
+    }
+    int st = CRDT_OK;
+    for (uint32_t j = 0; j < n_dst; ++j) {
+        st = crdt_merge_table(dsts[j], src, n_rows, since[j], wall, step, CRDT_MEM_DEVICE, &out[j]);
+        if (st >= 0 && win_mask && n_rows) {                  // (an error stores nothing: no bit)
+            k_fan_or_flags<<<std::min<uint32_t>(grid_for(n_rows, 256), 8192), 256, 0, d0->stream>>>(step, n_rows, j, wm);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipStreamSynchronize(d0->stream));         // (the next step writes step[] on another stream)
+        }
+        if (st != 0) {                                        // an exception (or an error) ends the sequence
+            for (uint32_t k = j + 1; k < n_dst; ++k) out[k] = cleared_result(dsts[k]->canonical);
+            break;
+        }
+    }
+    if (win_mask && n_rows) {
+        if (mask_mem == CRDT_MEM_HOST)
+            HIPCHK(hipMemcpyAsync(win_mask, wm, n_rows, hipMemcpyDeviceToHost, d0->stream));
+        HIPCHK(hipStreamSynchronize(d0->stream));
+    }
+    return st;
+}
+
+int crdt_fanout_tables(crdt_ctx* src, crdt_ctx* const* dsts, const int64_t* since_lt, uint32_t n_dst,
+                       uint64_t n_rows, int64_t wall, uint8_t* win_mask, int32_t mask_mem, crdt_result* out) {
+    if (!src || !dsts || !since_lt || !out || n_dst == 0 || n_dst > CRDT_FANOUT_MAX) return CRDT_E_INVALID;
+    for (uint32_t j = 0; j < n_dst; ++j)
+        if (!dsts[j]) return CRDT_E_INVALID;                  // (every null check before a ctx is read)
+    for (uint32_t j = 0; j < n_dst; ++j)
+        if (!tm_args_ok(dsts[j], src, win_mask != nullptr, mask_mem)) return CRDT_E_INVALID;
+    if (n_rows > src->cap) return CRDT_E_INVALID;
+    if (n_dst == 1) return crdt_merge_table(dsts[0], src, n_rows, since_lt[0], wall, win_mask, mask_mem, out);
+    crdt_ctx* d0 = dsts[0];
+    HIPCHK(hipSetDevice(d0->device));
+    // the composition: a destination switched to it or pinned to the sorted path (as crdt_merge_table), src
+    // among the destinations, or one of them twice (its merges are then not independent)
+    bool composed = false;
+    for (uint32_t j = 0; j < n_dst; ++j) {
+        crdt_ctx* d = dsts[j];
+        if (d->env_dynamic) read_env_knobs(d);
+        composed |= !d->table_merge || d == src || d->merge_path == CRDT_PATH_SORTED;
+        for (uint32_t k = 0; k < j; ++k) composed |= dsts[k] == d;
+    }
+    if (composed) return fanout_tables_composed(src, dsts, since_lt, n_dst, n_rows, wall, win_mask, mask_mem, out);
+    // src's rows are final before d0's stream reads them, and nothing is queued on a table it writes
+    HIPCHK(hipStreamSynchronize(src->stream));
+    for (uint32_t j = 1; j < n_dst; ++j) HIPCHK(hipStreamSynchronize(dsts[j]->stream));
+    FoArgs fa{};
+    uint64_t covered = 0;
+    for (uint32_t j = 0; j < n_dst; ++j) {
+        fa.dst[j] = dsts[j]->table;
+        fa.rows[j] = ex_rows(src, n_rows, since_lt[j]);
+        fa.cap[j] = dsts[j]->cap;
+        fa.since[j] = since_lt[j];
+        fa.canonical[j] = dsts[j]->canonical;
+        fa.rank[j] = dsts[j]->local_rank;
+        covered = std::max(covered, fa.rows[j]);
+    }
+    const unsigned nb = grid_for(covered, kTmTile);
+    uint8_t* rf;
+    int st;
+    if ((st = tm_stage_flags(d0, win_mask, mask_mem, n_rows, &rf))) return st;
+    if ((st = tm_begin(d0, nb, (int)n_dst))) return st;
+    // pass 1: src's {lt, rank, mod} once; every destination's counts, bits and clock words from it
+    if (covered) {
+        k_fo_clock<<<std::min(nb, kFoClockGrid), kTmThreads, 0, d0->stream>>>(
+            fa, n_dst, src->table, covered, nb, wall, d0->t_sel.p, d0->t_mask.p, d0->t_words.p);
+        HIPCHK(hipGetLastError());
+    }
+    unsigned long long w[kFoMax * kTmWords] = {};
+    if ((st = tm_read_words(d0, w, (int)n_dst))) return st;
+    // per destination: R_j = max(C_j, max lt of its selection), C_j' = Hlc.send(R_j).  A row that may raise in
+    // its recv(), a selected id outside it, or a send() that raises (the sequence ends there): nothing is
+    // written yet, the composition gives the exact stop point, exception details and error
+    crdt_result res[kFoMax];
+    bool has = false;
+    for (uint32_t j = 0; j < n_dst; ++j) {
+        const unsigned long long* wj = w + j * kTmWords;
+        composed |= wj[2] || (wj[3] && wj[1] > dsts[j]->cap);
+        has |= wj[3] != 0;
+        fa.stamp[j] = tm_recv_canonical(fa.canonical[j], wj);
+        res[j] = cleared_result(fa.canonical[j]);
+        res[j].n_stored = 1;
+        hlc_send(fa.stamp[j], wall).into(res[j]);
+        composed |= res[j].status != CRDT_OK;
+    }
+    if (composed) return fanout_tables_composed(src, dsts, since_lt, n_dst, n_rows, wall, win_mask, mask_mem, out);
+    ev_record(d0, kEvClock);
+    // pass 2: src's selected rows once, every destination's winners stored from them
+    HIPALLOC(d0->t_fcounts.ensure(kFanCounts));
+    HIPCHK(hipMemsetAsync(d0->t_fcounts.p, 0, kFanCounts * sizeof(unsigned long long), d0->stream));
+    if ((st = tm_zero_uncovered(d0, rf, has ? covered : 0, n_rows))) return st;
+    tm_apply_begin(d0, has);
+    if (has) {
+        k_fo_apply<<<nb, kTmThreads, 0, d0->stream>>>(fa, n_dst, src->table, covered, nb, d0->t_sel.p, d0->t_mask.p,
+                                                      d0->t_fcounts.p, rf);
+        HIPCHK(hipGetLastError());
+    }
+    tm_apply_end(d0, has);
+    if ((st = tm_flags_to_host(d0, win_mask, rf, mask_mem, n_rows))) return st;
+    std::vector<unsigned long long> counts(kFanCounts);
+    HIPCHK(hipMemcpyAsync(counts.data(), d0->t_fcounts.p, kFanCounts * sizeof(unsigned long long),
+                          hipMemcpyDeviceToHost, d0->stream));
+    HIPCHK(hipStreamSynchronize(d0->stream));
+    // per destination: its counts from the call's own words (no Misc slots: tm_finish sums none), its mark,
+    // its canonical C_j' and what crdt_last_plan reports
+    for (uint32_t j = 0; j < n_dst; ++j) {
+        const unsigned long long* cj = counts.data() + 2 * j * kCounterSlots;
+        for (int s = 0; s < kCounterSlots; ++s) {
+            res[j].n_present += cj[s];
+            res[j].n_won += cj[kCounterSlots + s];
+        }
+        tm_finish(dsts[j], &res[j], d0->h_misc, 0, 0, w + j * kTmWords, false);
+        dsts[j]->last_fanout = true;
+        out[j] = res[j];
+    }
+    collect_timing(d0);
+    return CRDT_OK;
+}
+
 int crdt_set_rank_bound(crdt_ctx* c, uint32_t bound) {
     if (!c) return CRDT_E_INVALID;
     c->rank_bound = bound;
@@ -4565,7 +4705,8 @@ int crdt_last_plan(const crdt_ctx* c, uint32_t* flags) {
     if (!c || !flags) return CRDT_E_INVALID;
     uint32_t f = 0;
     if (c->last_table) {
-        *flags = CRDT_PLAN_TABLE | (c->last_sync ? CRDT_PLAN_SYNC : 0u) | (c->last_fanin ? CRDT_PLAN_FANIN : 0u);
+        *flags = CRDT_PLAN_TABLE | (c->last_sync ? CRDT_PLAN_SYNC : 0u) | (c->last_fanin ? CRDT_PLAN_FANIN : 0u) |
+                 (c->last_fanout ? CRDT_PLAN_FANOUT : 0u);
         return CRDT_OK;
     }
     if (c->last_sorted) {

@@ -1,7 +1,8 @@
 // table_merge.inc — crdt_merge_table: dst.merge(src.recordMap(modifiedSince)) between two tables of one
 // device and one id space, without an export (crdt.dart:77-94 on the changeset of crdt.dart:157-160),
-// crdt_sync_tables, the two-way exchange on one read of both tables, and crdt_fanin_tables, up to eight
-// sources merged into one table on one read of it (both further down).
+// crdt_sync_tables, the two-way exchange on one read of both tables, crdt_fanin_tables, up to eight
+// sources merged into one table on one read of it, and crdt_fanout_tables, one source merged into up to
+// eight tables on one read of it (all further down).
 // Included from crdt_merge.hip inside its anonymous namespace, beside the export kernels.
 //
 // Key k lives in row k of BOTH tables, so the merge is an element-wise pass over two aligned arrays:
@@ -515,6 +516,225 @@ __global__ __launch_bounds__(kTmThreads) void k_fan_apply(FanArgs a, uint32_t n_
         const uint32_t b = (uint32_t)(won >> (q * 8)) & 0xFFu;
         if (b) store_hc(dst, i, r[q], make_uint2(rl[q], rv[q]));
         if (flags && i < n) flags[i] = (uint8_t)b;
+    }
+}
+
+// ---- crdt_fanout_tables: the hub's outbound half, for j < n_dst: dsts[j].merge(src.recordMap(since_j)),
+// n_dst <= kFoMax, on ONE read of src (DESIGN §6g).  The win decision reads no canonical clock, src is never
+// written and the destinations are independent, so the n_dst clock passes of the composition are the same
+// read of src done n_dst times, and so are its apply passes' reads of src's selected rows.  Scratch in
+// crdt_fanin_tables' layout with j the destination: sel[j * nb + tile], mask[(j * nb + tile) * kTmMaskWords
+// ..], words[4 j ..], counts[128 j ..].
+//   k_fo_clock  {lt, rank, mod} of every row of src below the largest of the destinations' row bounds, each
+//               line once whatever n_dst is; from the loaded rows, per destination j (a runtime loop, its
+//               arguments held one destination a lane and read with v_readlane): the selection ballot
+//               !(mod < since_j) of its rows below ITS bound into its mask words, its tile count, and its
+//               clock words (the candidate bit against destination j's canonical and rank).  A wave's count
+//               and largest id come from the ballots; a wave that selected for j folds them, its candidate
+//               bit and each thread's max ord64(lt) into LDS (eight TmClocks in registers, the loop unrolled,
+//               spilled SGPRs).  At the end each destination's LDS state goes through one TmClock::publish:
+//               at most four atomics per destination per workgroup.
+//   k_fo_apply  one workgroup per tile; a tile that no destination selected writes its zero mask bytes and
+//               returns.  Else a thread takes its selection bits of every destination that selected in the
+//               tile (one 64-bit word, as k_fan_apply), loads src's row in full ONCE for its rows that ANY
+//               destination selected (the others read row 0) and keeps them in registers.  The destinations
+//               follow in call order, a runtime loop with one destination's loads in flight at a time (one
+//               that selected nothing in the tile is skipped): the decision half of its selected rows, the
+//               plain rule (src wins iff the destination's row is invisible or hlc_gt(src, dst)), the winners
+//               stored {lt, rank, val, mod = R_j} with that destination's stride, bit j of the row's outcome
+//               byte, n_present / n_won into counts[] (as k_fan_apply's).  The byte goes to win_mask[row]
+//               once, after the loop.  Every row belongs to one thread.
+constexpr int kFoMax = 8;                        // CRDT_FANOUT_MAX: one outcome bit per destination in a byte
+constexpr unsigned kFoClockGrid = 2048;          // as kTmClockGrid
+static_assert(kFoMax == CRDT_FANOUT_MAX, "the header's bound");
+static_assert(kFoMax <= 8, "one mask bit per destination");
+static_assert(kFoMax == kFanMax, "counts[] is crdt_fanin_tables' (kFanCounts words)");
+
+struct FoArgs {                                  // by value: what the two kernels know of each destination
+    Table dst[kFoMax];
+    uint64_t rows[kFoMax];                       // its row bound: ex_rows(src, n_rows, since_j)
+    uint64_t cap[kFoMax];
+    int64_t since[kFoMax];
+    int64_t canonical[kFoMax];                   // at entry (k_fo_clock's candidate bit)
+    int64_t stamp[kFoMax];                       // R_j (k_fo_apply)
+    uint32_t rank[kFoMax];
+};
+
+__device__ inline unsigned long long fo_lane64(unsigned long long v, uint32_t l) {   // lane l's v (l wave-uniform)
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, (int)l);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), (int)l);
+    return ((unsigned long long)hi << 32) | lo;
+}
+
+__global__ __launch_bounds__(kTmThreads) void k_fo_clock(FoArgs a, uint32_t n_dst, Table src, uint64_t n,
+                                                         uint32_t nb, int64_t wall, uint32_t* __restrict__ sel,
+                                                         unsigned long long* __restrict__ mask,
+                                                         unsigned long long* __restrict__ words)
+{
+    __shared__ uint32_t s_cnt[2][kFoMax][4];     // per destination and wave: selected rows; one buffer per tile parity
+    __shared__ TmClockLds s_clock[kFoMax];
+    __shared__ unsigned long long s_mx[kFoMax][kTmThreads];   // per destination and thread: max ord64(lt) so far
+    __shared__ unsigned long long s_id[kFoMax][4];            // per destination and wave: 1 + its largest selected id,
+    __shared__ uint32_t s_sum[kFoMax][4], s_cand[kFoMax][4];  // its selected rows, whether it met a candidate
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    for (uint32_t j = 0; j < n_dst; ++j) {       // (a thread's own slots, and lane 0 its wave's: no barrier)
+        s_mx[j][threadIdx.x] = 0;
+        if (lane == 0) { s_id[j][w] = 0; s_sum[j][w] = 0; s_cand[j][w] = 0; }
+    }
+    // Lane l keeps destination (l & 7)'s arguments; the loop below takes destination j's from lane j
+    // (v_readlane: scalar loads of FoArgs inside the tile loop put their latency on every (tile, j) step).
+    const int al = lane & (kFoMax - 1);
+    const unsigned long long v_since = (unsigned long long)a.since[al], v_canon = (unsigned long long)a.canonical[al];
+    const unsigned long long v_rows = a.rows[al];
+    const uint32_t v_rank = a.rank[al];
+    uint32_t par = 0;
+    for (uint32_t tile = blockIdx.x; tile < nb; tile += gridDim.x, par ^= 1u) {
+        const uint64_t base = (uint64_t)tile * kTmTile;
+        uint4 h[kTmItems];
+        uint32_t ml[kTmItems];
+#pragma unroll
+        for (int q = 0; q < kTmItems; ++q) {
+            const uint64_t i = tm_row(base, q);
+            const uint64_t ic = i < n ? i : n - 1;
+            h[q] = load_hot(src, ic);
+            ml[q] = *reinterpret_cast<const uint32_t*>(row_ptr(src, ic) + 16);
+        }
+#pragma unroll 1
+        for (uint32_t j = 0; j < n_dst; ++j) {
+            const int64_t since = (int64_t)fo_lane64(v_since, j), cj = (int64_t)fo_lane64(v_canon, j);
+            const uint64_t nj = fo_lane64(v_rows, j);
+            const uint32_t rj = (uint32_t)__builtin_amdgcn_readlane((int)v_rank, (int)j);
+            unsigned long long mine = 0;         // lane q < 8: the ballot of wave-instruction q (one store for the eight)
+            unsigned long long* m = mask + ((uint64_t)j * nb + tile) * kTmMaskWords;
+            uint32_t cnt = 0;                    // (wave-uniform, as top: from the ballots)
+            unsigned long long top = 0, mx = 0;  // 1 + the wave's largest selected id; this thread's max ord64(lt)
+            bool c = false;
+#pragma unroll
+            for (int q = 0; q < kTmItems; ++q) {
+                const uint64_t i = tm_row(base, q);
+                const bool keep = i < nj && !(hot_mod(h[q], ml[q]) < since);
+                const unsigned long long b = __ballot(keep);
+                mine = lane == q ? b : mine;
+                cnt += (uint32_t)__popcll(b);
+                // (bit l of b is row base + q * 256 + w * 64 + l; q ascends, so the last assignment is the largest)
+                if (b) top = base + (uint64_t)q * kTmThreads + (uint64_t)w * 64 + (64 - __clzll((long long)b));
+                if (keep) {
+                    const unsigned long long o = ord64(hot_lt(h[q]));
+                    mx = o > mx ? o : mx;
+                    c |= recv_candidate(h[q], cj, rj, wall);
+                }
+            }
+            if (lane < kTmItems) m[lane * 4 + w] = mine;
+            if (lane == 0) s_cnt[par][j][w] = cnt;
+            if (cnt) {                           // (the whole wave)
+                const unsigned long long old = s_mx[j][threadIdx.x];
+                s_mx[j][threadIdx.x] = mx > old ? mx : old;
+                const bool cd = __ballot(c) != 0;
+                if (lane == 0) {
+                    s_id[j][w] = top > s_id[j][w] ? top : s_id[j][w];
+                    s_sum[j][w] += cnt;
+                    s_cand[j][w] |= cd ? 1u : 0u;
+                }
+            }
+        }
+        __syncthreads();                         // (the next tile writes the other buffer)
+        if (threadIdx.x < n_dst) {
+            const uint32_t* t = s_cnt[par][threadIdx.x];
+            sel[(uint64_t)threadIdx.x * nb + tile] = t[0] + t[1] + t[2] + t[3];
+        }
+    }
+#pragma unroll 1
+    for (uint32_t j = 0; j < n_dst; ++j) {       // each destination's words through a TmClock: lane 0 carries its wave's
+        TmClock clock;
+        clock.mx = s_mx[j][threadIdx.x];
+        clock.id = lane == 0 ? s_id[j][w] : 0;
+        clock.cnt = lane == 0 ? s_sum[j][w] : 0;
+        clock.cand = s_cand[j][w];
+        clock.publish(s_clock[j], words + j * kTmWords);
+    }
+}
+
+__global__ __launch_bounds__(kTmThreads) void k_fo_apply(FoArgs a, uint32_t n_dst, Table src, uint64_t n,
+                                                         uint32_t nb, const uint32_t* __restrict__ sel,
+                                                         const unsigned long long* __restrict__ mask,
+                                                         unsigned long long* __restrict__ counts,
+                                                         uint8_t* __restrict__ flags)
+{
+    __shared__ int s_pw[kFoMax][2][4];
+    const uint32_t tile = blockIdx.x;
+    const uint64_t base = (uint64_t)tile * kTmTile;
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // (wave-uniform: the mask words load as scalars)
+    // the destinations that selected in this tile (the counts load together), then this thread's selection bits
+    // of each of them, kept for the loop below: bit 8 j + q = destination j selected row q
+    uint32_t active = 0;
+#pragma unroll
+    for (int j = 0; j < kFoMax; ++j) {
+        const uint32_t cnt = sel[(uint64_t)((uint32_t)j < n_dst ? j : 0) * nb + tile];   // (always inside sel[])
+        active |= (uint32_t)((uint32_t)j < n_dst && cnt != 0) << j;
+    }
+    if (active == 0) {                           // the whole workgroup: no destination selected in this tile
+        tm_zero_flags(flags, base, n);
+        return;
+    }
+    unsigned long long bits = 0;
+    for (uint32_t j = 0; j < n_dst; ++j) {
+        if (!((active >> j) & 1u)) continue;
+        const unsigned long long* m = mask + ((uint64_t)j * nb + tile) * kTmMaskWords;
+        uint32_t b = 0;
+#pragma unroll
+        for (int q = 0; q < kTmItems; ++q) b |= (uint32_t)((m[q * 4 + w] >> lane) & 1ull) << q;
+        bits |= (unsigned long long)b << (8 * j);
+    }
+    uint32_t any = (uint32_t)bits | (uint32_t)(bits >> 32);   // the rows any destination selected
+    any |= any >> 16;
+    any |= any >> 8;
+    uint4 h[kTmItems];                           // src's rows, read once for all destinations
+    uint32_t v[kTmItems];
+#pragma unroll
+    for (int q = 0; q < kTmItems; ++q) {
+        // (the clock pass set bits of rows < n only; an unselected lane reads row 0: one hot line)
+        const uint64_t ic = (any >> q) & 1u ? tm_row(base, q) : 0;
+        h[q] = load_hot(src, ic);
+        v[q] = load_cold(src, ic).y;
+    }
+    unsigned long long won = 0;                  // byte q: the outcome byte of row q
+#pragma unroll 1
+    for (uint32_t j = 0; j < n_dst; ++j) {
+        if (!((active >> j) & 1u)) continue;     // (the whole workgroup)
+        const Table dst = a.dst[j];
+        const uint64_t nj = a.rows[j], dcap = a.cap[j];
+        const uint32_t mine = (uint32_t)(bits >> (8 * j));
+        uint4 d[kTmItems];
+        uint32_t keep = 0;
+#pragma unroll
+        for (int q = 0; q < kTmItems; ++q) {
+            const uint64_t i = tm_row(base, q);
+            // (the clock pass set bits of rows < nj only; the host sent a call with a selected id >= dcap elsewhere)
+            const bool k = ((mine >> q) & 1u) && i < nj && i < dcap;
+            keep |= (uint32_t)k << q;
+            d[q] = load_hot(dst, k ? i : 0);
+        }
+        const uint32_t st_hi = (uint32_t)((uint64_t)a.stamp[j] >> 32), st_lo = (uint32_t)a.stamp[j];
+        int npres = 0, nwon = 0;
+#pragma unroll
+        for (int q = 0; q < kTmItems; ++q) {
+            const bool k = (keep >> q) & 1u;
+            const bool present = (int32_t)d[q].w >= 0;
+            const bool win = k && (!present || hlc_gt(h[q], d[q]));
+            npres += k && present;
+            nwon += win;
+            if (win) store_hc(dst, tm_row(base, q), make_uint4(h[q].x, h[q].y, h[q].z, st_hi), make_uint2(st_lo, v[q]));
+            won |= (unsigned long long)win << (q * 8 + j);
+        }
+        unsigned long long* c = counts + (2 * j * kCounterSlots + (tile & (kCounterSlots - 1)));
+        tm_add_counts(npres, nwon, s_pw[j], c, c + kCounterSlots);
+    }
+    if (!flags) return;
+#pragma unroll
+    for (int q = 0; q < kTmItems; ++q) {
+        const uint64_t i = tm_row(base, q);
+        if (i < n) flags[i] = (uint8_t)(won >> (q * 8));
     }
 }
 

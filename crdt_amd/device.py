@@ -337,6 +337,30 @@ class DeviceTable:
             mask_arr = mask_arr[:n_rows]
         return [res[j].as_dict() for j in range(n_src)], mask_arr
 
+    def fanout_tables(self, dsts, n_rows: int, sinces, wall: int, win_mask=False):
+        """The hub's outbound half, called on the SOURCE: ``for d, since in zip(dsts, sinces):
+        d.merge(self.recordMap(modifiedSince: since))`` for up to ``_capi.FANOUT_MAX`` destination tables,
+        decided on one read of this table (``crdt_fanout_tables``); exactly what the ``merge_table`` calls leave,
+        the sequence ending at the first that raises.  Returns (list of result dicts, one per destination; mask
+        or None): ``mask[i]`` has bit j set where destination j stored row i.  ``win_mask``: as
+        ``merge_table``'s ``row_flags``."""
+        dsts, sinces = list(dsts), [int(s) for s in sinces]
+        if len(sinces) != len(dsts):
+            raise ValueError(f"fanout_tables: {len(dsts)} destinations but {len(sinces)} sinces")
+        for d in dsts:
+            if d.device != self.device:
+                raise ValueError(f"fanout_tables: a destination table is on device {d.device}, this one on {self.device}")
+        n_rows, n_dst = int(n_rows), len(dsts)
+        mask_arr, mptr, mem = self._row_flags_arg(win_mask, n_rows)
+        ctxs = (ctypes.c_void_p * max(n_dst, 1))(*(d._ctx.value for d in dsts))
+        since_arr = (ctypes.c_int64 * max(n_dst, 1))(*sinces)
+        res = (CrdtResult * max(n_dst, 1))()
+        st = self._lib.crdt_fanout_tables(self._ctx, ctxs, since_arr, n_dst, n_rows, int(wall), mptr, mem, res)
+        self._check(st, "crdt_fanout_tables")
+        if win_mask is True:
+            mask_arr = mask_arr[:n_rows]
+        return [res[j].as_dict() for j in range(n_dst)], mask_arr
+
     def clear_rows(self, first: int, count: int):
         self._check(self._lib.crdt_clear_rows(self._ctx, first, count), "crdt_clear_rows")
 
@@ -492,7 +516,7 @@ class DeviceTable:
                   "flagged": 1024, "ordered": 2048,
                   "combined": 4096, "route_l1": 8192, "route_tuned": 16384, "rl1_head": 262144,
                   "compact": 524288, "hot_direct": 1048576, "table": 2097152,
-                  "sync": 4194304, "fanin": 8388608}
+                  "sync": 4194304, "fanin": 8388608, "fanout": 16777216}
 
     def last_plan(self) -> dict:
         """crdt_last_plan: how the last merge ran ({'sorted': bool, 'packed': ..., ...})."""

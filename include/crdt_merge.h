@@ -337,6 +337,47 @@ int crdt_fanin_tables(crdt_ctx* dst, crdt_ctx* const* srcs, const int64_t* since
                       uint64_t n_rows, int64_t wall_millis, uint8_t* win_mask, int32_t mask_mem,
                       crdt_result* out /* [n_src] */);
 
+/* The hub's outbound half: for j in 0 .. n_dst-1: dsts[j].merge(src.recordMap(modifiedSince: since_lt[j])),
+ * 1 <= n_dst <= CRDT_FANOUT_MAX ctxs on the SAME device sharing one key / node / value interning.  For every
+ * input it leaves exactly what
+ *     for (j = 0; j < n_dst; ++j) {
+ *         s_j = crdt_merge_table(dsts[j], src, n_rows, since_lt[j], wall_millis, flags_j, mask_mem, &out[j]);
+ *         if (s_j != 0) break;
+ *     }
+ * leaves: every destination's rows and canonical, every field of every out[j], the return value (the first
+ * non-zero s_j, else 0) and the mask.  win_mask (optional, memory of kind mask_mem): [n_rows] bytes indexed by
+ * ROW id, every entry written: win_mask[i] = OR_j (flags_j[i] << j), bit j set where destination j stored row
+ * i.  After a stop at step j the destinations before j stay merged, dsts[k], k > j, is untouched, out[k] is
+ * zero except exc_index = UINT64_MAX and canonical_lt = dsts[k]'s own canonical, and no bit k > j is set.  An
+ * empty selection is still one merge() call on that destination: its closing Hlc.send advances its canonical.
+ * src is read-only (rows, canonical, plan, export view and high-water mark untouched, and every destination's
+ * export view too).  n_dst == 1 runs crdt_merge_table and reports its plan.
+ * The win decision (crdt.dart:83-84) reads no canonical clock, src is never written and the destinations are
+ * independent, so the whole call is decided on ONE read of src: one clock pass over {lt, rank, mod} of src's
+ * rows, every line once whatever n_dst is (per destination its tile counts, one selection bit per row and four
+ * words, the candidate bit against THAT destination's canonical and node id), one read-back of 4 * n_dst
+ * words, per destination R_j = max(C_j, max lt of selection j) and C_j' = Hlc.send(R_j), and one apply pass
+ * that skips the tiles no destination selected, loads src's selected rows once and, destination by
+ * destination, the decision half of its selected rows, and stores the winners with mod = R_j.  Scratch, on
+ * dsts[0]: 4 * n_dst words, n_dst counts per tile and n_dst bits per row, and the per-destination count
+ * words; nothing grows with the selection.
+ * The call runs the composition above itself, nothing written by then, whenever a row selected for
+ * destination j is a candidate for it (lt above dsts[j]'s canonical with its node id, or over 60000 ms ahead
+ * of wall_millis) or has an id >= dsts[j]'s capacity, any destination's Hlc.send raises, src is among the
+ * destinations, a destination appears twice, or any destination is pinned to CRDT_PATH_SORTED or was created
+ * under CRDT_TABLE_MERGE=0.
+ * CRDT_E_INVALID, nothing touched: a null src, dsts, since_lt, out or dsts[j] (checked before any ctx is
+ * read), n_dst == 0 or > CRDT_FANOUT_MAX, n_rows above src's capacity, a ctx on another device, a ctx joined
+ * to a communicator, a bad mask_mem with a mask pointer.  No ctx involved may be in another call; the work
+ * runs on dsts[0]'s stream after src's and every other destination's is drained, and the call is synchronous.
+ * After the fused form crdt_last_plan of EVERY destination is CRDT_PLAN_TABLE | CRDT_PLAN_FANOUT and
+ * crdt_last_path CRDT_PATH_GATHER (after a fallback: what each one's own crdt_merge_table reported);
+ * crdt_timing on dsts[0] gets scan_ms (the clock pass), apply_ms (the apply pass) and total_ms. */
+#define CRDT_FANOUT_MAX 8
+int crdt_fanout_tables(crdt_ctx* src, crdt_ctx* const* dsts, const int64_t* since_lt, uint32_t n_dst,
+                       uint64_t n_rows, int64_t wall_millis, uint8_t* win_mask, int32_t mask_mem,
+                       crdt_result* out /* [n_dst] */);
+
 /* ---- key-sharded multi-GPU (north star config 4) -------------
  * n_ranks ctxs — one per GPU, normally one process per GPU — form ONE replica whose
  * keys are sharded: rank d owns key k iff k % n_ranks == d and stores it at slot
@@ -492,8 +533,10 @@ enum crdt_plan_flags {
                                     form (table_merge.inc); set alone */
     CRDT_PLAN_SYNC = 4194304,     /* ... or, with CRDT_PLAN_TABLE, one side of a crdt_sync_tables that ran its
                                     fused two-way form (set on both ctxs) */
-    CRDT_PLAN_FANIN = 8388608     /* ... or, with CRDT_PLAN_TABLE, the destination of a crdt_fanin_tables that ran
+    CRDT_PLAN_FANIN = 8388608,    /* ... or, with CRDT_PLAN_TABLE, the destination of a crdt_fanin_tables that ran
                                     its fused form */
+    CRDT_PLAN_FANOUT = 16777216   /* ... or, with CRDT_PLAN_TABLE, a destination of a crdt_fanout_tables that ran
+                                    its fused form (set on every destination) */
 };
 int crdt_last_plan(const crdt_ctx* ctx, uint32_t* flags);
 
