@@ -118,6 +118,7 @@ SIGNATURES = {
     "crdt_export_read": (_INT, [_P, _U64, _U64, _P, _P, _P, _P, _P]),
     "crdt_export_release": (_INT, [_P]),
     "crdt_count_since": (_INT, [_P, _U64, _I64, _P, _P]),
+    "crdt_export_flagged": (_INT, [_P, _U64, _P, _I32, ctypes.c_uint8, _P]),
     "crdt_clear_rows": (_INT, [_P, _U64, _U64]),
     "crdt_remap_ranks": (_INT, [_P, _U64, _P, _U32]),
     "crdt_put_stamped": (_INT, [_P, _P, _P, _U64, _I64, _I32, _P]),

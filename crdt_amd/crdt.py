@@ -11,6 +11,8 @@ one device call (the hot path of the benchmark).
 """
 from __future__ import annotations
 
+import weakref
+
 import numpy as np
 
 from . import _capi
@@ -38,6 +40,44 @@ class Watch:
 
     def __len__(self):
         return len(self.events)
+
+
+FILL_LT = -0x7F7F7F7F7F7F7F80      # lt of a never-written row (bytes 0x80: DESIGN.md §2), outside the clock domain
+
+
+class _ReplicaGroup:
+    """The id space several ``MapCrdt``s of one device share (``MapCrdt.replica``): one key index, one
+    node ranking and one value store, which is what every table-to-table form asks of its ctxs.  Members are
+    held weakly; a ``MapCrdt`` that never calls ``replica()`` is a group of one."""
+
+    def __init__(self):
+        self.keys = KeyIndex()
+        self.nodes = NodeRanks()
+        self.values = ValueStore()
+        self._members: list = []
+
+    def add(self, member):
+        self._members.append(weakref.ref(member))
+
+    def members(self) -> list:
+        live = [(r, m) for r, m in ((r, r()) for r in self._members) if m is not None]
+        self._members = [r for r, _ in live]
+        return [m for _, m in live]
+
+    def register(self, node_ids):
+        """New node ids for every member: a shift of ranks re-ranks every member's rows, and every member's
+        local rank and rank bound follow."""
+        lut = self.nodes.register(node_ids)
+        members = self.members()
+        if lut is not None:
+            for m in members:
+                m._reserve()
+                m._table.remap_ranks(len(self.keys), lut)
+                m._table.local_rank = self.nodes.rank(m.nodeId)
+        for m in members:
+            if len(self.nodes) != m._rank_bound:      # ranks are dense: 0 .. len - 1
+                m._rank_bound = len(self.nodes)
+                m._table.set_rank_bound(m._rank_bound)
 
 
 class Crdt:
@@ -121,33 +161,45 @@ class MapCrdt(Crdt):
     """
 
     def __init__(self, nodeId, seed: dict | None = None, *, device: int = 0, capacity: int = 1024,
-                 clock=None):
+                 clock=None, _group: _ReplicaGroup | None = None):
         self.nodeId = nodeId
         self.clock = clock or now_millis
-        self._keys = KeyIndex()
-        self._nodes = NodeRanks()
-        self._values = ValueStore()
+        self._group = _group or _ReplicaGroup()
+        self._keys = self._group.keys
+        self._nodes = self._group.nodes
+        self._values = self._group.values
         self._hlc_override: dict = {}     # key id -> Hlc not in canonical (millis, counter) form
         self._mod_override: dict = {}     # key id -> modified Hlc with a foreign node / odd form
         self._watches: list = []
         self._rank_bound = 0
-        self._nodes.register([nodeId])
+        self.last_sync = None             # "table" | "object": how the last replica sync into this map ran
+        self.last_sync_winners = None     # winner records it fetched from the device (None: no export ran)
+        self._group.register([nodeId])    # (a shift of ranks reaches the members there are)
         self._table = DeviceTable(device, local_rank=self._nodes.rank(nodeId), capacity=capacity)
         self._table.set_rank_bound(len(self._nodes))
         self._rank_bound = len(self._nodes)
+        self._group.add(self)
         self.refreshCanonicalTime()
         if seed:
             self._store(list(seed.items()), notify=False)
 
+    def replica(self, nodeId, seed: dict | None = None, *, capacity: int | None = None, clock=None) -> "MapCrdt":
+        """A new ``MapCrdt`` on this one's device that shares its key ids, node ranks and value handles, with
+        a table, canonical clock, node id, watches and overrides of its own: the replicas of one group sync on
+        the device (``mergeFrom``, ``syncWith``, ``mergeFromAll``, ``broadcastTo``).  A node id equal to a
+        sibling's is allowed (a merge between the two then raises ``DuplicateNodeException``, as the
+        reference's does).  A group iterates its keys in the order the GROUP first saw them."""
+        cap = self._table.capacity if capacity is None else int(capacity)
+        return MapCrdt(nodeId, seed, device=self._table.device, capacity=cap, clock=clock or self.clock,
+                       _group=self._group)
+
     # ------------------------------------------------------------ internals
     def _register_nodes(self, node_ids):
-        lut = self._nodes.register(node_ids)
-        if lut is not None:
-            self._table.remap_ranks(len(self._keys), lut)
-            self._table.local_rank = self._nodes.rank(self.nodeId)
-        if len(self._nodes) != self._rank_bound:      # ranks are dense: 0 .. len - 1
-            self._rank_bound = len(self._nodes)
-            self._table.set_rank_bound(self._rank_bound)
+        self._group.register(node_ids)
+
+    def _shared(self) -> bool:
+        """Whether this map has live siblings (a group of one answers as a plain ``MapCrdt`` always has)."""
+        return len(self._group.members()) > 1
 
     def _reserve(self):
         if len(self._keys) > self._table.capacity:
@@ -194,8 +246,13 @@ class MapCrdt(Crdt):
 
     def _maybe_compact(self):
         if len(self._values) > 2 * max(4096, len(self._keys)):
-            _, _, val, _ = self._table.read_rows(np.arange(len(self._keys), dtype=np.uint32))
-            self._values.compact(val[val != NULL_HANDLE])
+            ids = np.arange(len(self._keys), dtype=np.uint32)
+            live = []
+            for m in self._group.members():             # several tables may hold one handle
+                m._reserve()
+                val = m._table.read_rows(ids)[2]
+                live.append(val[val != NULL_HANDLE])
+            self._values.compact(live[0] if len(live) == 1 else np.concatenate(live))
 
     def _raise_for(self, res: dict):
         st = res["status"]
@@ -215,6 +272,7 @@ class MapCrdt(Crdt):
     @property
     def length(self) -> int:                                            # crdt.dart:20 (map.length)
         """Live records counted on the device (crdt_count_since): no Record is built."""
+        self._reserve()
         return self._table.count_since(len(self._keys), 0)[1]
 
     @property
@@ -223,13 +281,22 @@ class MapCrdt(Crdt):
 
     # ------------------------------------------------------------ SPI
     def containsKey(self, key) -> bool:                                 # map_crdt.dart:21
-        return self._keys.get(key) is not None
+        kid = self._keys.get(key)
+        if kid is None or not self._shared():
+            return kid is not None
+        self._reserve()                                 # (a sibling may have interned the key)
+        return int(self._table.read_rows(np.array([kid], np.uint32))[0][0]) != FILL_LT
 
     def getRecord(self, key):                                           # map_crdt.dart:24
         kid = self._keys.get(key)
         if kid is None:
             return None
+        shared = self._shared()
+        if shared:
+            self._reserve()
         lt, rank, val, mod = self._table.read_rows(np.array([kid], np.uint32))
+        if shared and int(lt[0]) == FILL_LT:            # known to the group, never written here
+            return None
         return self._make_record(kid, lt[0], rank[0], val[0], mod[0])
 
     def putRecord(self, key, record: Record):                           # map_crdt.dart:27-30
@@ -240,6 +307,7 @@ class MapCrdt(Crdt):
 
     def recordMap(self, modifiedSince: Hlc | None = None) -> dict:      # map_crdt.dart:42-45
         since = modifiedSince.logicalTime if modifiedSince is not None else 0
+        self._reserve()
         ex = self._table.export_since(len(self._keys), since)       # one device compaction of all columns
         if ex.n == 0:
             return {}
@@ -269,6 +337,7 @@ class MapCrdt(Crdt):
         from . import hostlib
         from .crdt_json import _default
         since = modifiedSince.logicalTime if modifiedSince is not None else 0
+        self._reserve()
         ex = self._table.export_since(len(self._keys), since)
         if ex.n == 0:
             self.last_export = "native"
@@ -300,9 +369,11 @@ class MapCrdt(Crdt):
         return w
 
     def purge(self):                                                    # map_crdt.dart:52
+        self._reserve()
         self._table.clear_rows(0, len(self._keys))
-        self._keys.clear()
-        self._values.clear()
+        if not self._shared():                          # (a member clears its own rows and overrides only)
+            self._keys.clear()
+            self._values.clear()
         self._hlc_override.clear()
         self._mod_override.clear()
 
@@ -312,6 +383,7 @@ class MapCrdt(Crdt):
         return Hlc.fromLogicalTime(self._table.canonical, self.nodeId)
 
     def refreshCanonicalTime(self):                                     # crdt.dart:114-121
+        self._reserve()
         self._table.refresh_canonical(len(self._keys))
 
     # ------------------------------------------------------------ writes
@@ -499,3 +571,149 @@ class MapCrdt(Crdt):
         self._maybe_compact()
         self._raise_for(res)
         return res
+
+    # ------------------------------------------------------------ replica sync
+    # Each member below is DEFINED as a composition of merge() and recordMap() calls and leaves exactly what
+    # that composition leaves on every replica.  Between members of one group it runs as a table-to-table
+    # form on the device (include/crdt_merge.h); the records a merge stored are fetched (crdt_export_flagged
+    # on the SOURCE table, with the merge's row flags) only for a storing replica that has a watch or keeps
+    # an Hlc / modified on the host.  The object route is the composition itself: it is taken when a source
+    # keeps an Hlc outside the (millis << 16) + counter form (its millis is not lt >> 16, which the tables
+    # cannot see) or the replicas do not share a group.
+
+    @staticmethod
+    def _since_lt(h: Hlc | None) -> int:
+        return h.logicalTime if h is not None else 0
+
+    def _table_route(self, sources, others=()) -> bool:
+        """Whether a sync among self, ``sources`` and ``others`` runs on the device tables."""
+        everyone = [self, *sources, *others]
+        if any(m._table.device != self._table.device for m in everyone):
+            raise ValueError("replicas of different devices cannot sync")
+        return all(m._group is self._group for m in everyone) and not any(m._hlc_override for m in sources)
+
+    def _wants_winners(self) -> bool:
+        return bool(self._watches or self._hlc_override or self._mod_override)
+
+    def _took(self, src: "MapCrdt", n_rows: int, flags, bit: int):
+        """Bookkeeping of one stored table merge into self: the winners, read from src's table."""
+        self.last_sync = "table"
+        if flags is None:
+            return
+        ex = src._table.export_flagged(n_rows, flags, 1 << bit)
+        self.last_sync_winners = (self.last_sync_winners or 0) + ex.n
+        if ex.n == 0:
+            return
+        ids, _, _, val, _ = ex.columns()
+        if self._hlc_override or self._mod_override:
+            for k in ids.tolist():                      # canonical-form Hlc, modified by this node
+                self._hlc_override.pop(k, None)
+                self._mod_override.pop(k, None)
+        if self._watches:
+            keys, values = self._keys.keys, self._values
+            for k, v in zip(ids.tolist(), val.tolist()):
+                self._emit(keys[k], values.get(v))
+
+    def _sync_rows(self, *replicas) -> int:
+        n = len(self._keys)
+        for m in replicas:
+            m._reserve()
+            m.last_sync_winners = None
+        return n
+
+    def mergeFrom(self, src: "MapCrdt", modifiedSince: Hlc | None = None, wall: int | None = None):
+        """``self.merge(src.recordMap(modifiedSince=modifiedSince), wall=wall)``."""
+        wall = self._wall(wall)
+        if not self._table_route([src]):
+            self.last_sync, self.last_sync_winners = "object", None
+            return self.merge(src.recordMap(modifiedSince=modifiedSince), wall=wall)
+        n = self._sync_rows(self, src)
+        res, flags = self._table.merge_table(src._table, n, self._since_lt(modifiedSince), wall,
+                                             row_flags=self._wants_winners())
+        self.last_sync = "table"
+        if res["n_stored"]:
+            self._took(src, n, flags, 0)
+        self._maybe_compact()
+        self._raise_for(res)
+
+    def syncWith(self, other: "MapCrdt", sinceSelf: Hlc | None = None, sinceOther: Hlc | None = None,
+                 wall: int | None = None):
+        """``self.merge(other.recordMap(modifiedSince=sinceOther))`` then, unless that raised,
+        ``other.merge(self.recordMap(modifiedSince=sinceSelf))``, one ``wall`` for both.  The reference's
+        ``_sync(local, remote)`` is ``t = local.canonicalTime; remote.syncWith(local, sinceSelf=t)``."""
+        wall = self._wall(wall)
+        if not self._table_route([other, self]):
+            self.last_sync, self.last_sync_winners = "object", None
+            self.merge(other.recordMap(modifiedSince=sinceOther), wall=wall)
+            other.last_sync, other.last_sync_winners = "object", None
+            return other.merge(self.recordMap(modifiedSince=sinceSelf), wall=wall)
+        n = self._sync_rows(self, other)
+        (res_a, fl_a), (res_b, fl_b) = self._table.sync_tables(
+            other._table, n, self._since_lt(sinceSelf), self._since_lt(sinceOther), wall,
+            row_flags=(self._wants_winners(), other._wants_winners()))
+        self.last_sync = "table"
+        if res_a["n_stored"]:
+            self._took(other, n, fl_a, 0)               # other's copy of what self took is unchanged (a tie)
+        if res_a["status"] == 0:
+            other.last_sync = "table"
+            if res_b["n_stored"]:
+                other._took(self, n, fl_b, 0)           # self is not written after its own merge
+        self._maybe_compact()
+        self._raise_for(res_a)
+        other._raise_for(res_b)
+
+    def mergeFromAll(self, srcs, sinces=None, wall: int | None = None):
+        """``for s, t in zip(srcs, sinces): self.merge(s.recordMap(modifiedSince=t))``, ending at the first
+        that raises."""
+        wall = self._wall(wall)
+        srcs = list(srcs)
+        sinces = [None] * len(srcs) if sinces is None else list(sinces)
+        if len(sinces) != len(srcs):
+            raise ValueError(f"mergeFromAll: {len(srcs)} sources but {len(sinces)} sinces")
+        if not self._table_route(srcs):
+            self.last_sync, self.last_sync_winners = "object", None
+            for s, t in zip(srcs, sinces):
+                self.merge(s.recordMap(modifiedSince=t), wall=wall)
+            return
+        n = self._sync_rows(self, *srcs)
+        try:
+            for c in range(0, len(srcs), _capi.FANIN_MAX):      # a sequence: consecutive chunks are exact
+                part = srcs[c:c + _capi.FANIN_MAX]
+                res, mask = self._table.merge_tables([s._table for s in part], n,
+                                                     [self._since_lt(t) for t in sinces[c:c + len(part)]], wall,
+                                                     win_mask=self._wants_winners())
+                self.last_sync = "table"
+                for j, s in enumerate(part):
+                    if res[j]["n_stored"]:
+                        self._took(s, n, mask, j)
+                    self._raise_for(res[j])
+        finally:
+            self._maybe_compact()
+
+    def broadcastTo(self, dsts, sinces=None, wall: int | None = None):
+        """``for d, t in zip(dsts, sinces): d.merge(self.recordMap(modifiedSince=t))``, ending at the first
+        that raises."""
+        wall = self._wall(wall)
+        dsts = list(dsts)
+        sinces = [None] * len(dsts) if sinces is None else list(sinces)
+        if len(sinces) != len(dsts):
+            raise ValueError(f"broadcastTo: {len(dsts)} destinations but {len(sinces)} sinces")
+        if not self._table_route([self], dsts):
+            for d, t in zip(dsts, sinces):
+                d.last_sync, d.last_sync_winners = "object", None
+                d.merge(self.recordMap(modifiedSince=t), wall=wall)
+            return
+        n = self._sync_rows(self, *dsts)
+        try:
+            for c in range(0, len(dsts), _capi.FANOUT_MAX):
+                part = dsts[c:c + _capi.FANOUT_MAX]
+                res, mask = self._table.fanout_tables([d._table for d in part], n,
+                                                      [self._since_lt(t) for t in sinces[c:c + len(part)]], wall,
+                                                      win_mask=any(d._wants_winners() for d in part))
+                for j, d in enumerate(part):
+                    d.last_sync = "table"                   # (a later destination is never reached after a raise)
+                    if res[j]["n_stored"]:
+                        d._took(self, n, mask if d._wants_winners() else None, j)
+                    d._raise_for(res[j])
+        finally:
+            self._maybe_compact()

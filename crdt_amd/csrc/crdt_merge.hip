@@ -1674,6 +1674,123 @@ __global__ __launch_bounds__(kExThreads) void k_ex_write(Table table, uint64_t n
     }
 }
 
+// ---- flag-predicated export (crdt_export_flagged): the rows whose flag byte has one of `bits`, as the
+// same five columns, ascending by id — the winners of a table merge as a list.  k_ex_*'s tiles, scan and
+// capped grid; the predicate is the caller's byte per row instead of the row's mod.
+//   k_xf_count  the flag bytes alone (n bytes in all), eight rows a load: a thread takes bytes
+//               base + 8 tid .. + 7 of its tile (order does not matter to a count) -> counts[tile]
+//   k_ex_scan   as above -> offs[nb + 1], total in words[0]
+//   k_xf_write  a capped grid strides over the tiles; a tile whose count is 0 costs its two offsets.
+//               Another takes its flag bytes in the base + q * 256 + tid layout (ballot order is id order),
+//               loads both halves of its FLAGGED rows (the other lanes read row 0: one hot line, no branch
+//               around a load) and stores the five columns.  The live rows (val != CRDT_NULL_VALUE, which
+//               the count pass never sees) are summed in a register over the workgroup's tiles and go
+//               to words[1] in one atomic per workgroup.
+typedef uint32_t u32x2b __attribute__((ext_vector_type(2), aligned(1)));   // (a flags array starts anywhere)
+
+__device__ inline uint32_t xf_flagged8(uint64_t v, uint64_t m)              // bytes of v with a bit of m's byte
+{
+    const uint64_t y = v & m, lo7 = 0x7F7F7F7F7F7F7F7Full;
+    return (uint32_t)__popcll((((y & lo7) + lo7) | y) & ~lo7);
+}
+
+__global__ __launch_bounds__(kExThreads) void k_xf_count(const uint8_t* __restrict__ flags, uint64_t n,
+                                                         uint8_t bits, uint32_t nb, uint32_t* __restrict__ counts)
+{
+    __shared__ uint32_t s_c[2][4];               // per wave; one buffer per tile parity (as k_ex_count)
+    const uint64_t m = 0x0101010101010101ull * bits;
+    uint32_t par = 0;
+    for (uint32_t tile = blockIdx.x; tile < nb; tile += gridDim.x, par ^= 1u) {
+        const uint64_t i = (uint64_t)tile * kExTile + 8u * threadIdx.x;
+        uint64_t v = 0;
+        if (i + 8 <= n) {
+            const u32x2b t = *reinterpret_cast<const u32x2b*>(flags + i);
+            v = ((uint64_t)t.y << 32) | t.x;
+        } else {                                 // (the last tile's last bytes: nothing past flags[n - 1] is read)
+            for (uint64_t j = i; j < n; ++j) v |= (uint64_t)flags[j] << (8 * (j - i));
+        }
+        uint32_t c = xf_flagged8(v, m);
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off, 64);
+        if ((threadIdx.x & 63) == 0) s_c[par][threadIdx.x >> 6] = c;
+        __syncthreads();                         // (the next tile writes the other buffer)
+        if (threadIdx.x == 0) counts[tile] = s_c[par][0] + s_c[par][1] + s_c[par][2] + s_c[par][3];
+    }
+}
+
+__global__ __launch_bounds__(kExThreads) void k_xf_write(Table table, uint64_t n, const uint8_t* __restrict__ flags,
+                                                         uint8_t bits, uint32_t nb, const uint64_t* __restrict__ offs,
+                                                         uint32_t* __restrict__ key, int64_t* __restrict__ lt,
+                                                         uint32_t* __restrict__ rank, uint32_t* __restrict__ val,
+                                                         int64_t* __restrict__ mod,
+                                                         unsigned long long* __restrict__ words)
+{
+    __shared__ uint32_t s_cnt[kExItems * 4];
+    __shared__ uint32_t s_live[4];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    uint32_t live = 0;                           // this thread's, over the workgroup's tiles (< 2^32 rows each)
+    for (uint32_t tile = blockIdx.x; tile < nb; tile += gridDim.x) {
+        const uint64_t o0 = offs[tile];
+        if (offs[tile + 1] == o0) continue;       // the whole workgroup: nothing flagged in this tile
+        const uint64_t base = (uint64_t)tile * kExTile;
+        uint8_t f[kExItems];
+#pragma unroll
+        for (int q = 0; q < kExItems; ++q) {
+            const uint64_t i = base + q * kExThreads + threadIdx.x;
+            f[q] = flags[i < n ? i : n - 1];
+        }
+        uint4 h[kExItems];
+        uint2 x[kExItems];
+        uint32_t keep = 0;
+#pragma unroll
+        for (int q = 0; q < kExItems; ++q) {
+            const uint64_t i = base + q * kExThreads + threadIdx.x;
+            const bool k = i < n && (f[q] & bits);
+            keep |= (uint32_t)k << q;
+            const uint64_t ic = k ? i : 0;       // an unflagged lane reads row 0 (one hot line for all of them)
+            h[q] = load_hot(table, ic);
+            x[q] = load_cold(table, ic);
+        }
+        uint32_t before[kExItems];
+#pragma unroll
+        for (int q = 0; q < kExItems; ++q) {
+            const unsigned long long b = __ballot((keep >> q) & 1u);
+            before[q] = (uint32_t)__popcll(b & ((1ull << lane) - 1));
+            if (lane == 0) s_cnt[q * 4 + w] = (uint32_t)__popcll(b);
+        }
+        __syncthreads();
+        uint32_t run = 0;
+#pragma unroll
+        for (int q = 0; q < kExItems; ++q) {
+            uint32_t pre = run;
+#pragma unroll
+            for (int ww = 0; ww < 4; ++ww) {
+                const uint32_t cnt = s_cnt[q * 4 + ww];
+                pre += ww < w ? cnt : 0u;
+                run += cnt;
+            }
+            if ((keep >> q) & 1u) {
+                const uint64_t pos = o0 + pre + before[q];
+                key[pos] = (uint32_t)(base + q * kExThreads + threadIdx.x);
+                lt[pos] = (int64_t)(((uint64_t)h[q].y << 32) | h[q].x);
+                rank[pos] = h[q].z;
+                val[pos] = x[q].y;
+                mod[pos] = (int64_t)(((uint64_t)h[q].w << 32) | x[q].x);
+                live += x[q].y != CRDT_NULL_VALUE;
+            }
+        }
+        __syncthreads();                         // (s_cnt is the next tile's too)
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) live += __shfl_xor(live, off, 64);
+    if (lane == 0) s_live[w] = live;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const unsigned long long l = (unsigned long long)s_live[0] + s_live[1] + s_live[2] + s_live[3];
+        if (l) atomicAdd(&words[1], l);
+    }
+}
+
 #include "table_merge.inc"
 
 __global__ __launch_bounds__(256) void k_fill_i64(long long* __restrict__ p, uint64_t n, long long v)
@@ -3907,6 +4024,25 @@ static void ex_drop(crdt_ctx* c) {
     c->x_key.release(); c->x_rank.release(); c->x_val.release(); c->x_lt.release(); c->x_mod.release();
 }
 
+// Column buffers for total records: grown to fit, and given back first when they hold over four
+// times as many (a full export must not pin its gigabytes under the sparse deltas that follow it).
+static int ex_fit_columns(crdt_ctx* c, uint64_t total) {
+    auto ex_fit = [](auto& b, uint64_t n) {
+        if (b.p && b.n > 4 * std::max<uint64_t>(n, 1u << 16)) b.release();
+        return b.ensure(n);
+    };
+    hipError_t e = ex_fit(c->x_key, total);
+    if (e == hipSuccess) e = ex_fit(c->x_lt, total);
+    if (e == hipSuccess) e = ex_fit(c->x_rank, total);
+    if (e == hipSuccess) e = ex_fit(c->x_val, total);
+    if (e == hipSuccess) e = ex_fit(c->x_mod, total);
+    if (e != hipSuccess) {
+        ex_drop(c);
+        return e == hipErrorOutOfMemory ? CRDT_E_NOMEM : CRDT_E_HIP;
+    }
+    return CRDT_OK;
+}
+
 int crdt_count_since(crdt_ctx* c, uint64_t n_rows, int64_t since_lt, uint64_t* n, uint64_t* n_live) {
     if (!c || !n || !n_live || n_rows > c->cap) return CRDT_E_INVALID;
     *n = *n_live = 0;
@@ -3952,21 +4088,7 @@ int crdt_export_since(crdt_ctx* c, uint64_t n_rows, int64_t since_lt, crdt_expor
     const uint64_t total = w[0];
     if (total > rows) return CRDT_E_HIP;              // (never: the counts are of these rows)
     if (total) {
-        // column buffers for total records: grown to fit, and given back first when they hold over four
-        // times as many (a full export must not pin its gigabytes under the sparse deltas that follow it)
-        auto ex_fit = [](auto& b, uint64_t n) {
-            if (b.p && b.n > 4 * std::max<uint64_t>(n, 1u << 16)) b.release();
-            return b.ensure(n);
-        };
-        hipError_t e = ex_fit(c->x_key, total);
-        if (e == hipSuccess) e = ex_fit(c->x_lt, total);
-        if (e == hipSuccess) e = ex_fit(c->x_rank, total);
-        if (e == hipSuccess) e = ex_fit(c->x_val, total);
-        if (e == hipSuccess) e = ex_fit(c->x_mod, total);
-        if (e != hipSuccess) {
-            ex_drop(c);
-            return e == hipErrorOutOfMemory ? CRDT_E_NOMEM : CRDT_E_HIP;
-        }
+        if (int st = ex_fit_columns(c, total)) return st;
         k_ex_write<<<nb, kExThreads, 0, c->stream>>>(c->table, rows, since_lt, c->x_offs.p, c->x_key.p,
                                                      c->x_lt.p, c->x_rank.p, c->x_val.p, c->x_mod.p);
         HIPCHK(hipGetLastError());
@@ -3979,6 +4101,53 @@ int crdt_export_since(crdt_ctx* c, uint64_t n_rows, int64_t since_lt, crdt_expor
     }
     out->n = total;
     out->n_live = w[1];
+    c->x_n = total;
+    c->x_valid = true;
+    return CRDT_OK;
+}
+
+// The rows a table merge's flags name, as a changeset: crdt_export_since with the caller's byte per row
+// as the predicate.  No ex_rows clipping (the flags are the caller's: a flagged row at or above the
+// high-water mark is exported with its fill contents).
+int crdt_export_flagged(crdt_ctx* c, uint64_t n_rows, const uint8_t* flags, int32_t flags_mem, uint8_t bits,
+                        crdt_export* out) {
+    if (!c || !out || (n_rows && !flags) || n_rows > c->cap || c->has_comm || flags_mem != CRDT_MEM_DEVICE)
+        return CRDT_E_INVALID;
+    memset(out, 0, sizeof(*out));
+    out->mem = CRDT_MEM_DEVICE;
+    out->device = c->device;
+    c->x_valid = false;                               // the earlier view ends here, whatever follows
+    c->x_n = 0;
+    if (n_rows == 0 || bits == 0) { c->x_valid = true; return CRDT_OK; }
+    HIPCHK(hipSetDevice(c->device));
+    const unsigned nb = grid_for(n_rows, kExTile);
+    HIPALLOC(c->x_words.ensure(2));
+    HIPALLOC(c->x_counts.ensure(nb));
+    HIPALLOC(c->x_offs.ensure((size_t)nb + 1));
+    HIPCHK(hipMemsetAsync(c->x_words.p, 0, 2 * sizeof(unsigned long long), c->stream));
+    k_xf_count<<<std::min(nb, kExCountGrid), kExThreads, 0, c->stream>>>(flags, n_rows, bits, nb, c->x_counts.p);
+    k_ex_scan<<<1, kExScanStep, 0, c->stream>>>(c->x_counts.p, nb, c->x_offs.p, c->x_words.p);
+    HIPCHK(hipGetLastError());
+    unsigned long long total = 0, live = 0;
+    HIPCHK(hipMemcpyAsync(&total, c->x_words.p, sizeof(total), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (total > n_rows) return CRDT_E_HIP;            // (never: the counts are of these rows)
+    if (total) {                                      // (an empty selection: n_live = 0 without the write pass)
+        if (int st = ex_fit_columns(c, total)) return st;
+        k_xf_write<<<std::min(nb, kExCountGrid), kExThreads, 0, c->stream>>>(
+            c->table, n_rows, flags, bits, nb, c->x_offs.p, c->x_key.p, c->x_lt.p, c->x_rank.p, c->x_val.p,
+            c->x_mod.p, c->x_words.p);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(&live, c->x_words.p + 1, sizeof(live), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));      // drained: another ctx's stream may read the columns
+        out->key_id = c->x_key.p;
+        out->lt = c->x_lt.p;
+        out->rank = c->x_rank.p;
+        out->val = c->x_val.p;
+        out->mod = c->x_mod.p;
+    }
+    out->n = total;
+    out->n_live = live;
     c->x_n = total;
     c->x_valid = true;
     return CRDT_OK;

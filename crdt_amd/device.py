@@ -92,7 +92,7 @@ class _Cols:
 class Export:
     """A device-resident changeset (``crdt_export``): ``n`` records, ``n_live`` of them not
     tombstones.  It belongs to the table that exported it and ends at that table's next
-    ``export_since``, ``export_release`` or ``close``; a view that has ended raises
+    ``export_since``, ``export_flagged``, ``export_release`` or ``close``; a view that has ended raises
     ``CrdtNativeError(CRDT_E_INVALID)`` (the state is checked on the host, no memory is read)."""
 
     def __init__(self, table: "DeviceTable", view, serial: int):
@@ -221,6 +221,30 @@ class DeviceTable:
         v = _capi.CrdtExport()
         self._check(self._lib.crdt_export_since(self._ctx, int(n_rows), int(since), ctypes.byref(v)),
                     "crdt_export_since")
+        self._export_serial = getattr(self, "_export_serial", 0) + 1
+        return Export(self, v, self._export_serial)
+
+    def export_flagged(self, n_rows: int, flags, bits: int = 0xFF) -> "Export":
+        """The rows of [0, n_rows) whose ``flags[i] & bits`` is non-zero as one changeset, ascending by id
+        (``crdt_export_flagged``): the winners of a table merge, read from the table they came from with the
+        merge's row flags or mask.  ``flags``: a torch uint8/bool CUDA tensor of at least ``n_rows`` entries.
+        The view replaces this table's earlier one, as ``export_since``'s does."""
+        n_rows, bits = int(n_rows), int(bits)
+        if not 0 <= bits <= 0xFF:
+            raise ValueError(f"export_flagged: bits {bits:#x} is not a byte")
+        mem = _capi.CRDT_MEM_DEVICE
+        if _is_torch(flags) and flags.is_cuda:
+            if flags.numel() < n_rows:
+                raise ValueError("export_flagged: flags must hold one entry per row")
+            fptr = self._dptr(flags, "u1", "flags")
+        else:                                           # host memory: the library refuses it (CRDT_E_INVALID)
+            flags = np.ascontiguousarray(flags.numpy() if _is_torch(flags) else flags, dtype=np.uint8)
+            if len(flags) < n_rows:
+                raise ValueError("export_flagged: flags must hold one entry per row")
+            fptr, mem = flags.ctypes.data_as(ctypes.c_void_p), _capi.CRDT_MEM_HOST
+        v = _capi.CrdtExport()
+        self._check(self._lib.crdt_export_flagged(self._ctx, n_rows, fptr, mem, bits, ctypes.byref(v)),
+                    "crdt_export_flagged")
         self._export_serial = getattr(self, "_export_serial", 0) + 1
         return Export(self, v, self._export_serial)
 

@@ -171,7 +171,7 @@ int crdt_modified_since(crdt_ctx* ctx, uint64_t n_rows, int64_t since_lt, uint32
  *
  * Ownership: the columns belong to the ctx that exported them, in buffers of their own sized from the
  * count pass (not the staging crdt_merge / crdt_put_rows reuse).  They stay valid until the next
- * crdt_export_since, crdt_export_release or crdt_destroy on THAT ctx; calls on other ctxs, and merges
+ * crdt_export_since, crdt_export_flagged, crdt_export_release or crdt_destroy on THAT ctx; calls on other ctxs, and merges
  * or puts on the same ctx, leave them alone.  crdt_export_since is synchronous: the ctx's stream is
  * drained before it returns, so another ctx's stream may read the columns at once.  n_rows == 0 and an
  * empty selection give n = 0 (the pointers may then be NULL).
@@ -206,6 +206,36 @@ int crdt_export_release(crdt_ctx* ctx);
 /* The export's n and n_live alone: the count pass only, no column and nothing sized by the table is
  * allocated (Crdt.length = n_live at since_lt = 0, crdt.dart:20). */
 int crdt_count_since(crdt_ctx* ctx, uint64_t n_rows, int64_t since_lt, uint64_t* n, uint64_t* n_live);
+/* ---- flag-predicated export: "which records did that merge store?" as a changeset ----
+ * The rows of ctx in [0, n_rows) whose flags[i] & bits is non-zero, ascending by id, as the five columns
+ * of a crdt_export with n and n_live filled.  Ownership, lifetime and synchrony are crdt_export_since's:
+ * the columns live in the ctx's export buffers, the call ends the ctx's earlier view and becomes the
+ * current one (crdt_export_read / crdt_export_release work on it, the next crdt_export_since or
+ * crdt_export_flagged ends it), the stream is drained before return, and buffers over four times too
+ * large are given back first.  Rows are read as they are: a flagged row at or above the high-water mark
+ * is exported with its fill contents (the flags are the caller's; nothing is clipped).  The table's
+ * rows, canonical and high-water mark are untouched.  The passes: the flag bytes alone (n_rows bytes), a
+ * scan of the tile counts, and a write pass that loads only the flagged rows of the tiles that hold one.
+ *
+ * flags ([n_rows] bytes, CRDT_MEM_DEVICE, on the ctx's device) is read-only and may be NULL when n_rows
+ * is 0.  CRDT_E_INVALID, with nothing touched and the earlier view kept, for a NULL ctx, out or flags, n_rows
+ * above the capacity, a ctx joined to a communicator, and flags_mem == CRDT_MEM_HOST.  bits == 0 and
+ * n_rows == 0 give an empty valid view.
+ *
+ * Call it on the table the merged records CAME FROM, with the merge's flags: the stored record is the
+ * source's {lt, rank, val} (its mod in the destination is the destination's stamp, which the caller
+ * knows from the result), and the source is not written by the merge, while the destination's row may
+ * be overwritten again before anyone looks.
+ *   crdt_merge_table(dst, src, .., flags):  crdt_export_flagged(src, n_rows, flags, DEVICE, 1, &v) is
+ *       exactly the records dst stored: the reference's map after removeWhere (crdt.dart:80-85).
+ *   crdt_fanin_tables(dst, srcs, .., mask): bit j read against srcs[j] gives merge j's stored records,
+ *       even where a later merge of the call overwrote the row in dst.
+ *   crdt_fanout_tables(src, dsts, .., mask): bit j read against src gives destination j's.
+ *   crdt_sync_tables(a, b, .., flags_a, flags_b): flags_a reads against b and flags_b against a.  A row
+ *       that a took from b ties in the second merge (equal keeps local), so b's copy is unchanged where
+ *       flags_a is set; a is not written after the first merge, so it holds what b stored. */
+int crdt_export_flagged(crdt_ctx* ctx, uint64_t n_rows, const uint8_t* flags, int32_t flags_mem,
+                        uint8_t bits, crdt_export* out);
 /* purge() (map_crdt.dart:51-52) and rollback of interned-but-uncommitted ids. */
 int crdt_clear_rows(crdt_ctx* ctx, uint64_t first, uint64_t count);
 /* Re-rank stored node ids after the host inserts a new nodeId between existing
