@@ -63,7 +63,23 @@ class CrdtExport(ctypes.Structure):
                 ("n_live", ctypes.c_uint64), ("mem", ctypes.c_int32), ("device", ctypes.c_int32)]
 
 
-EXPORT_TILE = 2048                         # rows per workgroup of the export's passes (crdt_merge.hip kExTile)
+class CrdtDiff(ctypes.Structure):
+    _fields_ = [("n_a_ahead", ctypes.c_uint64), ("n_b_ahead", ctypes.c_uint64), ("n_conflict", ctypes.c_uint64),
+                ("n_visible_a", ctypes.c_uint64), ("n_visible_b", ctypes.c_uint64), ("first_diff", ctypes.c_uint64)]
+
+    def as_dict(self) -> dict:
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
+DIFF_A_AHEAD = 1                           # enum crdt_diff_bits: the bits of a crdt_diff_tables flag byte
+DIFF_B_AHEAD = 2
+DIFF_CONFLICT = 4
+DIFF_NONE = 0xFFFFFFFFFFFFFFFF             # crdt_diff.first_diff when no row differs
+DIGEST_ROWS = 0                            # enum crdt_digest_kind
+DIGEST_STATE = 1
+DIFF_GRID = 2048                           # workgroups of the diff and digest passes (table_diff.inc kDfGrid)
+
+EXPORT_TILE = 2048                      # rows per workgroup of the export's passes (crdt_merge.hip kExTile)
 EXPORT_SCAN_STEP = 1024                    # tile counts its scan takes per loop iteration (kExScanStep)
 EXPORT_COUNT_GRID = 2048                   # workgroups of its count pass, striding over the tiles (kExCountGrid)
 TABLE_TILE = 2048                          # rows per workgroup of crdt_merge_table's two passes (table_merge.inc kTmTile)
@@ -128,6 +144,8 @@ SIGNATURES = {
     "crdt_sync_tables": (_INT, [_P, _P, _U64, _I64, _I64, _I64, _P, _P, _I32, _P, _P]),
     "crdt_fanin_tables": (_INT, [_P, _P, _P, _U32, _U64, _I64, _P, _I32, _P]),
     "crdt_fanout_tables": (_INT, [_P, _P, _P, _U32, _U64, _I64, _P, _I32, _P]),
+    "crdt_diff_tables": (_INT, [_P, _P, _U64, _P, _I32, _P]),
+    "crdt_digest_rows": (_INT, [_P, _U64, _U64, _I32, _P, _I32]),
     "crdt_comm_unique_id": (_INT, [_P]),
     "crdt_comm_init_rccl": (_INT, [_P, _U32, _U32, _P]),
     "crdt_comm_init_ops": (_INT, [_P, _U32, _U32, _P]),

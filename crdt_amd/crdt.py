@@ -42,7 +42,27 @@ class Watch:
         return len(self.events)
 
 
-FILL_LT = -0x7F7F7F7F7F7F7F80      # lt of a never-written row (bytes 0x80: DESIGN.md §2), outside the clock domain
+class ReplicaDiff:
+    """What ``MapCrdt.diff`` found: the number of keys on which this map holds the winning record
+    (``ahead``), on which the other does (``behind``), and on which both hold one Hlc with different values
+    (``conflicts``: no merge heals those).  With ``keys=True`` also the three key lists (else None)."""
+
+    __slots__ = ("ahead", "behind", "conflicts", "ahead_keys", "behind_keys", "conflict_keys")
+
+    def __init__(self, ahead: int, behind: int, conflicts: int, ahead_keys=None, behind_keys=None,
+                 conflict_keys=None):
+        self.ahead, self.behind, self.conflicts = int(ahead), int(behind), int(conflicts)
+        self.ahead_keys, self.behind_keys, self.conflict_keys = ahead_keys, behind_keys, conflict_keys
+
+    @property
+    def converged(self) -> bool:
+        return self.ahead == 0 and self.behind == 0 and self.conflicts == 0
+
+    def __repr__(self):
+        return f"ReplicaDiff(ahead={self.ahead}, behind={self.behind}, conflicts={self.conflicts})"
+
+
+FILL_LT = -0x7F7F7F7F7F7F7F80     # lt of a never-written row (bytes 0x80: DESIGN.md §2), outside the clock domain
 
 
 class _ReplicaGroup:
@@ -174,6 +194,7 @@ class MapCrdt(Crdt):
         self._rank_bound = 0
         self.last_sync = None             # "table" | "object": how the last replica sync into this map ran
         self.last_sync_winners = None     # winner records it fetched from the device (None: no export ran)
+        self.last_diff = None             # "table" | "object": how this map's last diff() ran
         self._group.register([nodeId])    # (a shift of ranks reaches the members there are)
         self._table = DeviceTable(device, local_rank=self._nodes.rank(nodeId), capacity=capacity)
         self._table.set_rank_bound(len(self._nodes))
@@ -717,3 +738,76 @@ class MapCrdt(Crdt):
                     d._raise_for(res[j])
         finally:
             self._maybe_compact()
+
+    # ------------------------------------------------------------ replica comparison (read-only)
+    # diff() is DEFINED as the comparison of self.recordMap() with other.recordMap(): per key, a map is ahead
+    # when it alone holds a record or its record's Hlc is greater (the win rule of crdt.dart:83-84), and the
+    # key is a conflict when both hold one Hlc with values that differ (Record ==, record.dart:34-35).  Between
+    # members of one group that keep no Hlc on the host it runs on the two device tables (crdt_diff_tables):
+    # no Record is built and the flag bytes stay on the device.  None of these members emits a watch event,
+    # moves a clock, touches last_sync, or interns or compacts anything.
+
+    def diff(self, other: "MapCrdt", keys: bool = False) -> ReplicaDiff:
+        """Where this map and ``other`` stand: ``ahead`` (this map holds the winning record), ``behind``,
+        ``conflicts`` and ``converged``; ``keys=True`` adds the three key lists, in the group's key order."""
+        if other._group is not self._group or self._hlc_override or other._hlc_override:
+            self.last_diff = "object"
+            return self._diff_objects(other, keys)
+        self.last_diff = "table"
+        n = len(self._keys)
+        self._reserve()
+        other._reserve()
+        d, flags = self._table.diff_table(other._table, n, flags=keys)
+        n_conf, conf_ids = d["n_conflict"], None
+        if n_conf:
+            # the tables compare values by handle, and equal values may sit under two handles (the same
+            # record stored on both sides by putRecord or merge()): the definition compares the values
+            if flags is None:
+                d, flags = self._table.diff_table(other._table, n, flags=True)
+            ids, _, _, va, _ = self._table.export_flagged(n, flags, _capi.DIFF_CONFLICT).columns()
+            vb = other._table.export_flagged(n, flags, _capi.DIFF_CONFLICT).columns()[3]
+            get = self._values.get
+            real = np.fromiter((a != b and get(a) != get(b) for a, b in zip(va.tolist(), vb.tolist())), bool, len(ids))
+            conf_ids, n_conf = ids[real], int(real.sum())
+        if not keys:
+            return ReplicaDiff(d["n_a_ahead"], d["n_b_ahead"], n_conf)
+        names = self._keys.keys
+
+        def listed(bit, count):
+            if not count:
+                return []
+            return [names[i] for i in self._table.export_flagged(n, flags, bit).columns()[0].tolist()]
+
+        return ReplicaDiff(d["n_a_ahead"], d["n_b_ahead"], n_conf, listed(_capi.DIFF_A_AHEAD, d["n_a_ahead"]),
+                           listed(_capi.DIFF_B_AHEAD, d["n_b_ahead"]),
+                           [names[i] for i in conf_ids.tolist()] if n_conf else [])
+
+    def _diff_objects(self, other: "MapCrdt", keys: bool) -> ReplicaDiff:
+        """The definition itself, on the two recordMap()s."""
+        ra, rb = self.recordMap(), other.recordMap()
+        order = list(ra) + [k for k in rb if k not in ra]
+        if other._group is self._group:
+            order.sort(key=self._keys.get)
+        ahead, behind, conflicts = [], [], []
+        for k in order:
+            a, b = ra.get(k), rb.get(k)
+            if b is None or (a is not None and a.hlc > b.hlc):
+                ahead.append(k)
+            elif a is None or b.hlc > a.hlc:
+                behind.append(k)
+            elif a.value != b.value:
+                conflicts.append(k)
+        if not keys:
+            return ReplicaDiff(len(ahead), len(behind), len(conflicts))
+        return ReplicaDiff(len(ahead), len(behind), len(conflicts), ahead, behind, conflicts)
+
+    def convergedWith(self, other: "MapCrdt") -> bool:
+        """Whether ``self.recordMap() == other.recordMap()`` under ``Record ==`` (``diff(other).converged``)."""
+        return self.diff(other).converged
+
+    def stateDigest(self, block_rows: int = 1 << 20) -> np.ndarray:
+        """One uint64 word per ``block_rows`` key ids of what ``recordMap()`` holds under ``Record ==``
+        (``DeviceTable.digest_rows(state=True)``).  Members of one group whose ``diff`` reports nothing on
+        the device tables have equal words; values enter by their handle in the group's value store."""
+        self._reserve()
+        return self._table.digest_rows(len(self._keys), block_rows, state=True)

@@ -1792,6 +1792,7 @@ __global__ __launch_bounds__(kExThreads) void k_xf_write(Table table, uint64_t n
 }
 
 #include "table_merge.inc"
+#include "table_diff.inc"
 
 __global__ __launch_bounds__(256) void k_fill_i64(long long* __restrict__ p, uint64_t n, long long v)
 {
@@ -1976,6 +1977,7 @@ struct crdt_ctx {
     DBuf<uint8_t> t_wflags;
     DBuf<uint8_t> t_fstep, t_fmask;    // crdt_fanin_tables' composition: one step's row flags, a host mask's staging
     DBuf<unsigned long long> t_fcounts; // its fused form: the sources' striped n_present / n_won (k_fan_apply)
+    DBuf<unsigned long long> df_words;  // crdt_diff_tables' six words / crdt_digest_rows' words for host memory (table_diff.inc)
     bool table_merge = true;           // CRDT_TABLE_MERGE=0: every crdt_merge_table takes the composition
     bool last_table = false;           // the last merge on this ctx ran the fused table form
     bool last_sync = false;            // ... as one side of a fused crdt_sync_tables
@@ -3763,7 +3765,7 @@ void crdt_destroy(crdt_ctx* c) {
     c->s_millis.release(); c->s_mod.release(); c->s_flags.release(); c->s_out.release();
     c->x_key.release(); c->x_rank.release(); c->x_val.release(); c->x_lt.release(); c->x_mod.release();
     c->x_counts.release(); c->x_offs.release(); c->x_words.release();
-    c->t_sel.release(); c->t_words.release(); c->t_mask.release(); c->t_wflags.release();
+    c->t_sel.release(); c->t_words.release(); c->t_mask.release(); c->t_wflags.release(); c->df_words.release();
     c->t_fstep.release(); c->t_fmask.release(); c->t_fcounts.release();
     c->d_word.release();
     c->d_ibase.release();
@@ -4843,6 +4845,63 @@ int crdt_fanout_tables(crdt_ctx* src, crdt_ctx* const* dsts, const int64_t* sinc
         out[j] = res[j];
     }
     collect_timing(d0);
+    return CRDT_OK;
+}
+
+// ---- crdt_diff_tables / crdt_digest_rows: the read-only comparison and the block digests (table_diff.inc)
+int crdt_diff_tables(crdt_ctx* a, crdt_ctx* b, uint64_t n_rows, uint8_t* diff_flags, int32_t flags_mem,
+                     crdt_diff* out) {
+    if (!a || !b || !out) return CRDT_E_INVALID;      // (before any ctx is read)
+    if (!tm_args_ok(a, b, diff_flags != nullptr, flags_mem) || n_rows > a->cap || n_rows > b->cap)
+        return CRDT_E_INVALID;
+    crdt_diff d = {0, 0, 0, 0, 0, UINT64_MAX};
+    if (n_rows == 0) { *out = d; return CRDT_OK; }
+    HIPCHK(hipSetDevice(a->device));
+    if (b != a) HIPCHK(hipStreamSynchronize(b->stream));   // b's rows are final before a's stream reads them
+    uint8_t* df;
+    int st;
+    if ((st = tm_stage_flags(a, diff_flags, flags_mem, n_rows, &df))) return st;
+    HIPALLOC(a->df_words.ensure(kDfWords));
+    HIPCHK(hipMemsetAsync(a->df_words.p, 0, (kDfWords - 1) * sizeof(unsigned long long), a->stream));
+    HIPCHK(hipMemsetAsync(a->df_words.p + kDfWords - 1, 0xFF, sizeof(unsigned long long), a->stream));
+    const unsigned nb = grid_for(n_rows, kTmTile);
+    k_df_diff<<<std::min(nb, kDfGrid), kTmThreads, 0, a->stream>>>(a->table, b->table, n_rows, nb, df,
+                                                                   a->df_words.p);
+    HIPCHK(hipGetLastError());
+    if ((st = tm_flags_to_host(a, diff_flags, df, flags_mem, n_rows))) return st;
+    unsigned long long w[kDfWords];
+    HIPCHK(hipMemcpyAsync(w, a->df_words.p, sizeof(w), hipMemcpyDeviceToHost, a->stream));
+    HIPCHK(hipStreamSynchronize(a->stream));
+    *out = {w[0], w[1], w[2], w[3], w[4], w[5]};
+    return CRDT_OK;
+}
+
+int crdt_digest_rows(crdt_ctx* c, uint64_t n_rows, uint64_t block_rows, int32_t kind, uint64_t* out_words,
+                     int32_t mem) {
+    if (!c || (n_rows && !out_words) || n_rows > c->cap || c->has_comm || block_rows < (uint64_t)kTmTile ||
+        (block_rows & (block_rows - 1)) || (kind != CRDT_DIGEST_ROWS && kind != CRDT_DIGEST_STATE) ||
+        (mem != CRDT_MEM_HOST && mem != CRDT_MEM_DEVICE))
+        return CRDT_E_INVALID;
+    if (n_rows == 0) return CRDT_OK;
+    HIPCHK(hipSetDevice(c->device));
+    const uint64_t n_words = (n_rows + block_rows - 1) / block_rows;
+    unsigned long long* dw = reinterpret_cast<unsigned long long*>(out_words);
+    if (mem == CRDT_MEM_HOST) {
+        HIPALLOC(c->df_words.ensure(std::max<uint64_t>(n_words, kDfWords)));
+        dw = c->df_words.p;
+    }
+    HIPCHK(hipMemsetAsync(dw, 0, n_words * sizeof(unsigned long long), c->stream));
+    const unsigned nb = grid_for(n_rows, kTmTile);
+    // tiles per block, as a shift (nb < 2^32: from 31 on every tile is in block 0)
+    const uint32_t shift = std::min<uint32_t>((uint32_t)__builtin_ctzll(block_rows / kTmTile), 31u);
+    if (kind == CRDT_DIGEST_STATE)
+        k_df_digest<true><<<std::min(nb, kDfGrid), kTmThreads, 0, c->stream>>>(c->table, n_rows, nb, shift, dw);
+    else
+        k_df_digest<false><<<std::min(nb, kDfGrid), kTmThreads, 0, c->stream>>>(c->table, n_rows, nb, shift, dw);
+    HIPCHK(hipGetLastError());
+    if (mem == CRDT_MEM_HOST)
+        HIPCHK(hipMemcpyAsync(out_words, dw, n_words * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
     return CRDT_OK;
 }
 

@@ -385,6 +385,39 @@ class DeviceTable:
             mask_arr = mask_arr[:n_rows]
         return [res[j].as_dict() for j in range(n_dst)], mask_arr
 
+    def diff_table(self, other: "DeviceTable", n_rows: int, flags=False):
+        """The read-only comparison of this replica (a) with ``other`` (b) over rows [0, n_rows)
+        (``crdt_diff_tables``): neither table, clock, export view or plan is touched.  Returns (dict of
+        ``n_a_ahead, n_b_ahead, n_conflict, n_visible_a, n_visible_b, first_diff``; flags or None): the flags
+        hold one byte per ROW id, ``_capi.DIFF_A_AHEAD`` where this table holds the winning record,
+        ``DIFF_B_AHEAD`` where ``other`` does, ``DIFF_CONFLICT`` where both hold one (lt, rank) with different
+        values, and feed ``export_flagged``.  ``flags``: as ``merge_table``'s ``row_flags``."""
+        if other.device != self.device:
+            raise ValueError(f"diff_table: the other table is on device {other.device}, this one on {self.device}")
+        n_rows = int(n_rows)
+        flags_arr, fptr, mem = self._row_flags_arg(flags, n_rows)
+        d = _capi.CrdtDiff()
+        self._check(self._lib.crdt_diff_tables(self._ctx, other._ctx, n_rows, fptr, mem, ctypes.byref(d)),
+                    "crdt_diff_tables")
+        if flags is True:
+            flags_arr = flags_arr[:n_rows]
+        return d.as_dict(), flags_arr
+
+    def digest_rows(self, n_rows: int, block_rows: int = 1 << 20, state: bool = False) -> np.ndarray:
+        """One uint64 word per ``block_rows`` rows of [0, n_rows), computed on the device
+        (``crdt_digest_rows``).  ``state=False``: every row as stored, the words of ``bench.row_digests`` at
+        the default block.  ``state=True``: what ``Record ==`` sees (invisible rows count for nothing, ``mod``
+        is left out), equal for two replicas whenever ``diff_table`` reports no difference."""
+        n_rows, block_rows = int(n_rows), int(block_rows)
+        if block_rows <= 0:
+            raise CrdtNativeError(_capi.CRDT_E_INVALID, "crdt_digest_rows")
+        out = np.zeros(-(-n_rows // block_rows) if n_rows > 0 else 0, np.uint64)
+        kind = _capi.DIGEST_STATE if state else _capi.DIGEST_ROWS
+        self._check(self._lib.crdt_digest_rows(self._ctx, n_rows, block_rows, kind,
+                                               out.ctypes.data_as(ctypes.c_void_p), _capi.CRDT_MEM_HOST),
+                    "crdt_digest_rows")
+        return out
+
     def clear_rows(self, first: int, count: int):
         self._check(self._lib.crdt_clear_rows(self._ctx, first, count), "crdt_clear_rows")
 

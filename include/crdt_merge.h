@@ -233,7 +233,10 @@ int crdt_count_since(crdt_ctx* ctx, uint64_t n_rows, int64_t since_lt, uint64_t*
  *   crdt_fanout_tables(src, dsts, .., mask): bit j read against src gives destination j's.
  *   crdt_sync_tables(a, b, .., flags_a, flags_b): flags_a reads against b and flags_b against a.  A row
  *       that a took from b ties in the second merge (equal keeps local), so b's copy is unchanged where
- *       flags_a is set; a is not written after the first merge, so it holds what b stored. */
+ *       flags_a is set; a is not written after the first merge, so it holds what b stored.
+ *   crdt_diff_tables(a, b, .., diff_flags): CRDT_DIFF_A_AHEAD read against a is the changeset b lacks (what
+ *       b.merge(a.recordMap()) would store), CRDT_DIFF_B_AHEAD read against b the one a lacks, and
+ *       CRDT_DIFF_CONFLICT read against either gives that side's records of the rows no merge can heal. */
 int crdt_export_flagged(crdt_ctx* ctx, uint64_t n_rows, const uint8_t* flags, int32_t flags_mem,
                         uint8_t bits, crdt_export* out);
 /* purge() (map_crdt.dart:51-52) and rollback of interned-but-uncommitted ids. */
@@ -407,6 +410,55 @@ int crdt_fanin_tables(crdt_ctx* dst, crdt_ctx* const* srcs, const int64_t* since
 int crdt_fanout_tables(crdt_ctx* src, crdt_ctx* const* dsts, const int64_t* since_lt, uint32_t n_dst,
                        uint64_t n_rows, int64_t wall_millis, uint8_t* win_mask, int32_t mask_mem,
                        crdt_result* out /* [n_dst] */);
+
+/* ---- read-only comparison of two replicas: "are they converged, and if not, who is ahead on which rows?" ----
+ * For two ctxs on the SAME device sharing one key / node / value interning.  Per row i of [0, n_rows), with
+ * va = (mod_a >= 0) and vb likewise (the visibility of recordMap() and of the table forms at since = 0) and
+ * hlc = (lt, rank) compared as the merges compare it (signed lt, then unsigned rank):
+ *   CRDT_DIFF_A_AHEAD  iff va && (!vb || hlc_a > hlc_b): exactly the win rule of b.merge(a.recordMap())
+ *                      (crdt.dart:83-84).  For every input diff_flags[i] & 1 is the row_flags[i] that
+ *                      crdt_merge_table(b, a, n_rows, 0, ..) would write and n_a_ahead its n_won, whenever
+ *                      that merge does not raise.
+ *   CRDT_DIFF_B_AHEAD  the same with a and b swapped.
+ *   CRDT_DIFF_CONFLICT iff va && vb && hlc_a == hlc_b && val_a != val_b: the divergence no merge heals (equal
+ *                      keeps local on both sides).  Values are compared by handle.
+ *   else 0: both rows invisible (never written, cleared, above the high-water mark: their contents are not
+ *           compared), or both visible with equal hlc and val, what Record == sees (record.dart:34-35).  mod is
+ *           never compared: replicas stamp their own.
+ * diff_flags (optional, memory of kind flags_mem, any alignment): [n_rows] bytes indexed by ROW id, every entry
+ * written.  They feed crdt_export_flagged (its list above).  *out: the rows carrying each bit, the visible
+ * rows of each side, and the smallest row id with a non-zero byte.
+ * Untouched: both tables' rows, canonicals, high-water marks and export views, crdt_last_plan, crdt_last_path
+ * and crdt_timing.  a == b is allowed (all zero); n_rows == 0 gives a zero struct with first_diff = UINT64_MAX.
+ * One streaming pass over both tables (table_diff.inc); its scratch is six words (and, for flags in host
+ * memory, the ctx's flag staging).  CRDT_E_INVALID, nothing touched: a null ctx or out (checked before any
+ * ctx is read), n_rows above either capacity, different devices, a ctx joined to a communicator, a bad
+ * flags_mem with a flags pointer.  Neither ctx may be in another call; the work runs on a's stream after b's
+ * is drained, and the call is synchronous. */
+enum crdt_diff_bits { CRDT_DIFF_A_AHEAD = 1, CRDT_DIFF_B_AHEAD = 2, CRDT_DIFF_CONFLICT = 4 };
+typedef struct crdt_diff {
+    uint64_t n_a_ahead, n_b_ahead, n_conflict;   /* rows carrying each bit */
+    uint64_t n_visible_a, n_visible_b;           /* rows of [0, n_rows) with mod >= 0 */
+    uint64_t first_diff;                         /* smallest row id with a non-zero byte; UINT64_MAX: none */
+} crdt_diff;
+int crdt_diff_tables(crdt_ctx* a, crdt_ctx* b, uint64_t n_rows, uint8_t* diff_flags, int32_t flags_mem,
+                     crdt_diff* out);
+
+/* One 64-bit word per block of rows: word k is the wrapping sum of mix(i, row_i) over the rows i of
+ * [k * block_rows, min((k + 1) * block_rows, n_rows)), ceil(n_rows / block_rows) words in all, with
+ *     h = lt * P0 ^ mod * P1 ^ ((rank << 32 | val) * P2) ^ (i * P3);  h ^= h >> 29;  h *= P4;  h ^= h >> 32
+ *     P0..P4 = 0x9E3779B97F4A7C15, 0xC2B2AE3D27D4EB4F, 0x165667B19E3779F9, 0xD6E8FEB86659FD93, 0xFF51AFD7ED558CCD
+ * CRDT_DIGEST_ROWS takes every row as stored, the never-written fill included: a table compares with rows held
+ * elsewhere without being read.  CRDT_DIGEST_STATE is the digest of what Record == sees: an invisible row
+ * (mod < 0) contributes 0 and a visible one leaves the mod term out, so two tables of one id space have equal
+ * STATE words whenever crdt_diff_tables reports all zeros, whatever their capacities, row sizes, stamps and
+ * never-written rows.  out_words (memory of kind mem; 8-byte aligned device memory) may be NULL when n_rows is 0.
+ * Read-only as crdt_diff_tables is.  CRDT_E_INVALID: a null ctx, a null out_words with n_rows > 0, n_rows above
+ * the capacity, block_rows not a power of two or below 2048 (a kernel tile never straddles two blocks), a bad
+ * kind or mem, a ctx joined to a communicator.  Synchronous. */
+enum crdt_digest_kind { CRDT_DIGEST_ROWS = 0, CRDT_DIGEST_STATE = 1 };
+int crdt_digest_rows(crdt_ctx* ctx, uint64_t n_rows, uint64_t block_rows, int32_t kind,
+                     uint64_t* out_words, int32_t mem /* of out_words */);
 
 /* ---- key-sharded multi-GPU (north star config 4) -------------
  * n_ranks ctxs — one per GPU, normally one process per GPU — form ONE replica whose
