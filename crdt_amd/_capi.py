@@ -138,6 +138,8 @@ SIGNATURES = {
     "crdt_clear_rows": (_INT, [_P, _U64, _U64]),
     "crdt_remap_ranks": (_INT, [_P, _U64, _P, _U32]),
     "crdt_put_stamped": (_INT, [_P, _P, _P, _U64, _I64, _I32, _P]),
+    "crdt_tombstone_live": (_INT, [_P, _U64, _I64, _P, _I32, _P]),
+    "crdt_export_live": (_INT, [_P, _U64, _P]),
     "crdt_refresh_canonical": (_INT, [_P, _U64, _P]),
     "crdt_merge": (_INT, [_P, _P, _I64, _P, _P]),
     "crdt_merge_table": (_INT, [_P, _P, _U64, _I64, _I64, _P, _I32, _P]),

@@ -195,6 +195,7 @@ class MapCrdt(Crdt):
         self.last_sync = None             # "table" | "object": how the last replica sync into this map ran
         self.last_sync_winners = None     # winner records it fetched from the device (None: no export ran)
         self.last_diff = None             # "table" | "object": how this map's last diff() ran
+        self.last_clear = None            # "table": the last clear() ran on the device table
         self._group.register([nodeId])    # (a shift of ranks reaches the members there are)
         self._table = DeviceTable(device, local_rank=self._nodes.rank(nodeId), capacity=capacity)
         self._table.set_rank_bound(len(self._nodes))
@@ -299,6 +300,32 @@ class MapCrdt(Crdt):
     @property
     def isEmpty(self) -> bool:                                          # crdt.dart:17
         return self.length == 0
+
+    def _live_columns(self):
+        """(key ids, value handles) of the live records in id order (crdt_export_live), as lists."""
+        self._reserve()
+        ex = self._table.export_live(len(self._keys))
+        if ex.n == 0:
+            return [], []
+        ids, _, _, val, _ = ex.columns()
+        return ids.tolist(), val.tolist()
+
+    @property
+    def map(self) -> dict:                                              # crdt.dart:22-24
+        """The live records' values, compacted on the device: no Record and no Hlc is built."""
+        ids, val = self._live_columns()
+        names, get = self._keys.keys, self._values.get
+        return {names[i]: get(v) for i, v in zip(ids, val)}
+
+    @property
+    def keys(self) -> list:                                             # crdt.dart:26
+        names = self._keys.keys
+        return [names[i] for i in self._live_columns()[0]]
+
+    @property
+    def values(self) -> list:                                           # crdt.dart:29
+        get = self._values.get
+        return [get(v) for v in self._live_columns()[1]]
 
     # ------------------------------------------------------------ SPI
     def containsKey(self, key) -> bool:                                 # map_crdt.dart:21
@@ -431,6 +458,31 @@ class MapCrdt(Crdt):
             self._mod_override.pop(int(i), None)
         for k, v in items:
             self._emit(k, v)
+        self._maybe_compact()
+
+    def clear(self, purge: bool = False, wall: int | None = None):      # crdt.dart:67-73
+        """``putAll`` of ``None`` over ``self.map``, decided and stored on the table (crdt_tombstone_live): one
+        ``Hlc.send``, every live record becomes a tombstone, and nothing moves when there is none.  The ids
+        of the cleared keys are fetched (crdt_export_flagged on this map's own table) only for a map that has
+        a watch or keeps an Hlc / modified on the host.  In a replica group a key that only siblings have
+        written is not live here and stays unwritten."""
+        if purge:
+            return self.purge()
+        wall = self._wall(wall)
+        self._reserve()
+        n = len(self._keys)
+        res, flags = self._table.tombstone_live(n, wall, row_flags=self._wants_winners())
+        self.last_clear = "table"
+        self._raise_for(res)
+        if res["n_won"] and flags is not None:
+            ids = self._table.export_flagged(n, flags, 1).columns()[0].tolist()
+            for k in ids:                               # canonical-form Hlc, modified by this node
+                self._hlc_override.pop(k, None)
+                self._mod_override.pop(k, None)
+            if self._watches:
+                keys = self._keys.keys
+                for k in ids:                           # id order: the order self.map iterates
+                    self._emit(keys[k], None)
         self._maybe_compact()
 
     # ------------------------------------------------------------ merge

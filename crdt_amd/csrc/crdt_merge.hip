@@ -1540,7 +1540,9 @@ typedef uint32_t u32x3u __attribute__((ext_vector_type(3), aligned(4)));
 // A capped grid strides over the tiles and each workgroup sums its live rows (and, for crdt_count_since:
 // counts == nullptr, its selected rows) in a register, so the atomics on words[] are two per workgroup,
 // not two per tile (one per tile measured 0.8 ms at 65536 tiles: same-address atomics serialise).
+// kLive (crdt_export_live): the selection is the live rows alone, so the two counts are one.
 constexpr unsigned kExCountGrid = 2048;          // 256 CUs x 8 resident workgroups
+template <bool kLive = false>
 __global__ __launch_bounds__(kExThreads) void k_ex_count(Table table, uint64_t n, int64_t since, uint32_t nb,
                                                          uint32_t* __restrict__ counts,
                                                          unsigned long long* __restrict__ words)
@@ -1561,7 +1563,7 @@ __global__ __launch_bounds__(kExThreads) void k_ex_count(Table table, uint64_t n
         for (int q = 0; q < kExItems; ++q) {
             const uint64_t i = base + q * kExThreads + threadIdx.x;
             const int64_t mod = (int64_t)(((uint64_t)v[q].x << 32) | v[q].y);
-            const bool keep = i < n && !(mod < since);
+            const bool keep = i < n && !(mod < since) && (!kLive || v[q].z != CRDT_NULL_VALUE);
             cl += (uint32_t)keep + ((uint32_t)(keep && v[q].z != CRDT_NULL_VALUE) << 16);
         }
 #pragma unroll
@@ -1620,6 +1622,7 @@ __global__ __launch_bounds__(kExScanStep) void k_ex_scan(const uint32_t* __restr
     if (tid == 0) { offs[nb] = s_carry; words[0] = s_carry; }
 }
 
+template <bool kLive = false>
 __global__ __launch_bounds__(kExThreads) void k_ex_write(Table table, uint64_t n, int64_t since,
                                                          const uint64_t* __restrict__ offs,
                                                          uint32_t* __restrict__ key, int64_t* __restrict__ lt,
@@ -1646,7 +1649,7 @@ __global__ __launch_bounds__(kExThreads) void k_ex_write(Table table, uint64_t n
     for (int q = 0; q < kExItems; ++q) {
         const uint64_t i = base + q * kExThreads + threadIdx.x;
         const int64_t m = (int64_t)(((uint64_t)h[q].w << 32) | x[q].x);
-        const bool k = i < n && !(m < since);
+        const bool k = i < n && !(m < since) && (!kLive || x[q].y != CRDT_NULL_VALUE);
         const unsigned long long b = __ballot(k);
         before[q] = (uint32_t)__popcll(b & ((1ull << lane) - 1));
         if (lane == 0) s_cnt[q * 4 + w] = (uint32_t)__popcll(b);
@@ -1793,6 +1796,7 @@ __global__ __launch_bounds__(kExThreads) void k_xf_write(Table table, uint64_t n
 
 #include "table_merge.inc"
 #include "table_diff.inc"
+#include "table_live.inc"
 
 __global__ __launch_bounds__(256) void k_fill_i64(long long* __restrict__ p, uint64_t n, long long v)
 {
@@ -3937,6 +3941,58 @@ int crdt_put_stamped(crdt_ctx* c, const uint32_t* key_id, const uint32_t* val, u
     return CRDT_OK;
 }
 
+// ---- crdt_tombstone_live: Crdt.clear() (crdt.dart:67-73) on the table (table_live.inc).  What
+// crdt_export_since at 0, a filter on val and crdt_put_stamped of the live ids leave, in one pass: Hlc.send is
+// taken first, the pass stores its stamp over the live rows, and the canonical moves only if there was one
+// (no live row: nothing was written, the no-op of crdt.dart:48).  A send that raises stores nothing: whether
+// it is reported depends on a live row alone, so the count pass answers it.
+static int tm_stage_flags(crdt_ctx* c, uint8_t* flags, int32_t flags_mem, uint64_t n_rows, uint8_t** dev);
+static int tm_flags_to_host(crdt_ctx* c, uint8_t* flags, const uint8_t* dev, int32_t flags_mem, uint64_t n_rows);
+static uint64_t ex_rows(const crdt_ctx* c, uint64_t n_rows, int64_t since);
+
+int crdt_tombstone_live(crdt_ctx* c, uint64_t n_rows, int64_t wall, uint8_t* row_flags, int32_t flags_mem,
+                        crdt_result* out) {
+    if (!c || !out || n_rows > c->cap || c->has_comm ||
+        (row_flags && flags_mem != CRDT_MEM_HOST && flags_mem != CRDT_MEM_DEVICE))
+        return CRDT_E_INVALID;
+    crdt_result res = cleared_result(c->canonical);
+    HIPCHK(hipSetDevice(c->device));
+    uint8_t* rf;
+    int st;
+    if ((st = tm_stage_flags(c, row_flags, flags_mem, n_rows, &rf))) return st;
+    const uint64_t rows = ex_rows(c, n_rows, 0);      // (the rows from the high-water mark on are fill: not live)
+    const HlcSend send = hlc_send(c->canonical, wall);
+    unsigned long long live = 0;
+    if (send.status != CRDT_OK) {
+        uint64_t n_sel = 0, n_live = 0;
+        if ((st = crdt_count_since(c, n_rows, 0, &n_sel, &n_live))) return st;
+        live = n_live;
+        if (rf && n_rows) HIPCHK(hipMemsetAsync(rf, 0, n_rows, c->stream));
+    } else {
+        unsigned long long* word = reinterpret_cast<unsigned long long*>(c->d_word.p);
+        if (rows) {
+            HIPCHK(hipMemsetAsync(word, 0, sizeof(*word), c->stream));
+            const unsigned nb = grid_for(rows, kTmTile);
+            k_lv_tombstone<<<std::min(nb, kLvGrid), kTmThreads, 0, c->stream>>>(c->table, rows, nb, send.canonical,
+                                                                                c->local_rank, rf, word);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpyAsync(&live, word, sizeof(live), hipMemcpyDeviceToHost, c->stream));
+        }
+        if (rf && n_rows > rows) HIPCHK(hipMemsetAsync(rf + rows, 0, n_rows - rows, c->stream));
+    }
+    if ((st = tm_flags_to_host(c, row_flags, rf, flags_mem, n_rows))) return st;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (live && send.status != CRDT_OK) {
+        send.into(res);
+    } else if (live) {
+        c->canonical = send.canonical;
+        res.canonical_lt = send.canonical;
+        res.n_won = live;
+    }
+    *out = res;
+    return res.status;
+}
+
 int crdt_read_rows(crdt_ctx* c, const uint32_t* key_id, uint64_t n, int64_t* lt, uint32_t* rank,
                    uint32_t* val, int64_t* mod, int32_t mem) {
     if (!c) return CRDT_E_INVALID;
@@ -4054,8 +4110,8 @@ int crdt_count_since(crdt_ctx* c, uint64_t n_rows, int64_t since_lt, uint64_t* n
     HIPALLOC(c->x_words.ensure(2));
     HIPCHK(hipMemsetAsync(c->x_words.p, 0, 2 * sizeof(unsigned long long), c->stream));
     const unsigned nb = grid_for(rows, kExTile);
-    k_ex_count<<<std::min(nb, kExCountGrid), kExThreads, 0, c->stream>>>(c->table, rows, since_lt, nb, nullptr,
-                                                                         c->x_words.p);
+    k_ex_count<false><<<std::min(nb, kExCountGrid), kExThreads, 0, c->stream>>>(c->table, rows, since_lt, nb,
+                                                                                nullptr, c->x_words.p);
     HIPCHK(hipGetLastError());
     unsigned long long w[2] = {0, 0};
     HIPCHK(hipMemcpyAsync(w, c->x_words.p, sizeof(w), hipMemcpyDeviceToHost, c->stream));
@@ -4065,7 +4121,8 @@ int crdt_count_since(crdt_ctx* c, uint64_t n_rows, int64_t since_lt, uint64_t* n
     return CRDT_OK;
 }
 
-int crdt_export_since(crdt_ctx* c, uint64_t n_rows, int64_t since_lt, crdt_export* out) {
+// crdt_export_since, and crdt_export_live (live: the selection's tombstones left out): one body.
+static int ex_export(crdt_ctx* c, uint64_t n_rows, int64_t since_lt, bool live, crdt_export* out) {
     if (!c || !out || n_rows > c->cap) return CRDT_E_INVALID;
     memset(out, 0, sizeof(*out));
     out->mem = CRDT_MEM_DEVICE;
@@ -4080,8 +4137,12 @@ int crdt_export_since(crdt_ctx* c, uint64_t n_rows, int64_t since_lt, crdt_expor
     HIPALLOC(c->x_counts.ensure(nb));
     HIPALLOC(c->x_offs.ensure((size_t)nb + 1));
     HIPCHK(hipMemsetAsync(c->x_words.p, 0, 2 * sizeof(unsigned long long), c->stream));
-    k_ex_count<<<std::min(nb, kExCountGrid), kExThreads, 0, c->stream>>>(c->table, rows, since_lt, nb,
-                                                                         c->x_counts.p, c->x_words.p);
+    if (live)
+        k_ex_count<true><<<std::min(nb, kExCountGrid), kExThreads, 0, c->stream>>>(c->table, rows, since_lt, nb,
+                                                                                   c->x_counts.p, c->x_words.p);
+    else
+        k_ex_count<false><<<std::min(nb, kExCountGrid), kExThreads, 0, c->stream>>>(c->table, rows, since_lt, nb,
+                                                                                    c->x_counts.p, c->x_words.p);
     k_ex_scan<<<1, kExScanStep, 0, c->stream>>>(c->x_counts.p, nb, c->x_offs.p, c->x_words.p);
     HIPCHK(hipGetLastError());
     unsigned long long w[2] = {0, 0};
@@ -4091,8 +4152,12 @@ int crdt_export_since(crdt_ctx* c, uint64_t n_rows, int64_t since_lt, crdt_expor
     if (total > rows) return CRDT_E_HIP;              // (never: the counts are of these rows)
     if (total) {
         if (int st = ex_fit_columns(c, total)) return st;
-        k_ex_write<<<nb, kExThreads, 0, c->stream>>>(c->table, rows, since_lt, c->x_offs.p, c->x_key.p,
-                                                     c->x_lt.p, c->x_rank.p, c->x_val.p, c->x_mod.p);
+        if (live)
+            k_ex_write<true><<<nb, kExThreads, 0, c->stream>>>(c->table, rows, since_lt, c->x_offs.p, c->x_key.p,
+                                                               c->x_lt.p, c->x_rank.p, c->x_val.p, c->x_mod.p);
+        else
+            k_ex_write<false><<<nb, kExThreads, 0, c->stream>>>(c->table, rows, since_lt, c->x_offs.p, c->x_key.p,
+                                                                c->x_lt.p, c->x_rank.p, c->x_val.p, c->x_mod.p);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(c->stream));      // drained: another ctx's stream may read the columns
         out->key_id = c->x_key.p;
@@ -4106,6 +4171,15 @@ int crdt_export_since(crdt_ctx* c, uint64_t n_rows, int64_t since_lt, crdt_expor
     c->x_n = total;
     c->x_valid = true;
     return CRDT_OK;
+}
+
+int crdt_export_since(crdt_ctx* c, uint64_t n_rows, int64_t since_lt, crdt_export* out) {
+    return ex_export(c, n_rows, since_lt, false, out);
+}
+
+// The map getter's rows (crdt.dart:23): the export at since = 0 without its tombstones.
+int crdt_export_live(crdt_ctx* c, uint64_t n_rows, crdt_export* out) {
+    return ex_export(c, n_rows, 0, true, out);
 }
 
 // The rows a table merge's flags name, as a changeset: crdt_export_since with the caller's byte per row

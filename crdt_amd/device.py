@@ -248,6 +248,15 @@ class DeviceTable:
         self._export_serial = getattr(self, "_export_serial", 0) + 1
         return Export(self, v, self._export_serial)
 
+    def export_live(self, n_rows: int) -> "Export":
+        """The ``map`` getter's rows (``crdt_export_live``): the records of ``export_since(n_rows, 0)`` that
+        are not tombstones, in the same order, so ``n == n_live``.  The view replaces this table's earlier
+        one, as ``export_since``'s does."""
+        v = _capi.CrdtExport()
+        self._check(self._lib.crdt_export_live(self._ctx, int(n_rows), ctypes.byref(v)), "crdt_export_live")
+        self._export_serial = getattr(self, "_export_serial", 0) + 1
+        return Export(self, v, self._export_serial)
+
     def count_since(self, n_rows: int, since: int) -> tuple[int, int]:
         """(records, live records) export_since would select; the count pass alone."""
         n, live = ctypes.c_uint64(), ctypes.c_uint64()
@@ -439,6 +448,23 @@ class DeviceTable:
         self._check(self._lib.crdt_put_stamped(self._ctx, c.ptrs["key"], c.ptrs["val"], len(key), int(wall),
                                                c.mem, ctypes.byref(res)), "crdt_put_stamped")
         return res.as_dict()
+
+    def tombstone_live(self, n_rows: int, wall: int, row_flags=False):
+        """``clear()`` on the table (``crdt_tombstone_live``): one ``Hlc.send`` at ``wall``, then every live row
+        of [0, n_rows) (visible and not a tombstone) becomes the tombstone ``{C, local rank, null, C}``, in one
+        pass over the table; exactly what ``export_since(n_rows, 0)``, a filter on ``val`` and ``put_stamped``
+        of the live ids leave, this table's export view untouched.  No live row: nothing moves, whatever the
+        wall.  Returns (result dict, row flags or None): the flags are indexed by ROW id, one byte for each of
+        ``n_rows`` rows, 1 where the row was tombstoned (they feed ``export_flagged`` on this table).
+        ``row_flags``: as ``merge_table``'s."""
+        n_rows = int(n_rows)
+        flags_arr, fptr, mem = self._row_flags_arg(row_flags, n_rows)
+        res = CrdtResult()
+        st = self._lib.crdt_tombstone_live(self._ctx, n_rows, int(wall), fptr, mem, ctypes.byref(res))
+        self._check(st, "crdt_tombstone_live")
+        if row_flags is True:
+            flags_arr = flags_arr[:n_rows]
+        return res.as_dict(), flags_arr
 
     def _batch(self, key, lt, rank, val, offsets, millis):
         c = _Cols(self.device, key=(key, "u4"), lt=(lt, "i8"), rank=(rank, "u4"), val=(val, "u4"), millis=(millis, "i8"))

@@ -236,7 +236,9 @@ int crdt_count_since(crdt_ctx* ctx, uint64_t n_rows, int64_t since_lt, uint64_t*
  *       flags_a is set; a is not written after the first merge, so it holds what b stored.
  *   crdt_diff_tables(a, b, .., diff_flags): CRDT_DIFF_A_AHEAD read against a is the changeset b lacks (what
  *       b.merge(a.recordMap()) would store), CRDT_DIFF_B_AHEAD read against b the one a lacks, and
- *       CRDT_DIFF_CONFLICT read against either gives that side's records of the rows no merge can heal. */
+ *       CRDT_DIFF_CONFLICT read against either gives that side's records of the rows no merge can heal.
+ *   crdt_tombstone_live(ctx, .., row_flags): read against ctx itself, key_id holds the ids of the watch()
+ *       events of that clear(), in id order (every such record is the tombstone {C, local node, null, C}). */
 int crdt_export_flagged(crdt_ctx* ctx, uint64_t n_rows, const uint8_t* flags, int32_t flags_mem,
                         uint8_t bits, crdt_export* out);
 /* purge() (map_crdt.dart:51-52) and rollback of interned-but-uncommitted ids. */
@@ -250,6 +252,38 @@ int crdt_remap_ranks(crdt_ctx* ctx, uint64_t n_rows, const uint32_t* old_to_new,
  * whole call, then rows {C, local_rank, val, C}; n == 0 is a no-op (crdt.dart:48). */
 int crdt_put_stamped(crdt_ctx* ctx, const uint32_t* key_id, const uint32_t* val, uint64_t n,
                      int64_t wall_millis, int32_t mem, crdt_result* out);
+
+/* clear() (crdt.dart:67-73: putAll of null over the live view) on the table itself.  A row i of [0, n_rows) is
+ * visible iff !(mod < 0) on the raw signed 64-bit value (crdt_export_since's predicate at since_lt = 0) and
+ * live iff it is visible and val != CRDT_NULL_VALUE.  For every input the call leaves exactly what
+ *     crdt_export_since(ctx, n_rows, 0, &v);
+ *     ids = { v.key_id[x] : v.val[x] != CRDT_NULL_VALUE }                 (v.n_live of them, ascending)
+ *     crdt_put_stamped(ctx, ids, {CRDT_NULL_VALUE, ..}, v.n_live, wall_millis, CRDT_MEM_DEVICE, out);
+ * leaves: the table's rows byte for byte (the zero padding of 32-B rows included), the canonical, every field
+ * of *out and the return status.  No live row: a no-op (crdt.dart:48), CRDT_OK and the canonical where it was
+ * even when Hlc.send at wall_millis would raise.  Hlc.send raises and there is a live row: status 1 or 3,
+ * nothing stored, the canonical unchanged.  Otherwise every live row becomes {lt = C, rank = the local rank,
+ * mod = C, val = CRDT_NULL_VALUE} with C = Hlc.send(canonical, wall_millis), the canonical becomes C and n_won
+ * is the number of live rows.  Unlike the composition it leaves the ctx's export view alone and allocates
+ * nothing that grows with the table or the selection: one streaming pass reads 12 B of every row below the
+ * high-water mark (every line of the table once) and stores the live ones whole; its scratch is one word
+ * (and, for flags in host memory, the ctx's flag staging).  When Hlc.send raises the pass is
+ * crdt_count_since's, which writes nothing.
+ * Untouched: every row that is not live (tombstones, invisible rows whatever their val, rows at or above
+ * n_rows, the never-written fill), the high-water mark (only rows below it can be live), crdt_last_plan,
+ * crdt_last_path and crdt_timing.
+ * row_flags (optional, memory of kind flags_mem, any alignment): [n_rows] bytes indexed by ROW id, every entry
+ * written: 1 where the row was tombstoned, else 0; all zero after a raise or a no-op.  They feed
+ * crdt_export_flagged on the same ctx (its list above).
+ * CRDT_E_INVALID, nothing touched: a null ctx or out, n_rows above the capacity, a bad flags_mem with a flags
+ * pointer, a ctx joined to a communicator.  Synchronous on the ctx's stream. */
+int crdt_tombstone_live(crdt_ctx* ctx, uint64_t n_rows, int64_t wall_millis, uint8_t* row_flags,
+                        int32_t flags_mem, crdt_result* out);
+/* The map getter's rows (crdt.dart:23): the records of crdt_export_since(ctx, n_rows, 0, ..) whose val !=
+ * CRDT_NULL_VALUE, in the same order, so n == n_live.  The same three passes with the second predicate;
+ * ownership, lifetime, synchrony and error cases are crdt_export_since's, and it becomes the ctx's current
+ * view (crdt_export_read / crdt_export_release work on it). */
+int crdt_export_live(crdt_ctx* ctx, uint64_t n_rows, crdt_export* out);
 
 /* refreshCanonicalTime (crdt.dart:114-121) over rows [0, n_rows). */
 int crdt_refresh_canonical(crdt_ctx* ctx, uint64_t n_rows, int64_t* out_lt);
