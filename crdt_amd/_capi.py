@@ -71,6 +71,13 @@ class CrdtDiff(ctypes.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+class CrdtPurge(ctypes.Structure):
+    _fields_ = [("n_candidates", ctypes.c_uint64), ("n_purged", ctypes.c_uint64)]
+
+    def as_dict(self) -> dict:
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
 DIFF_A_AHEAD = 1                           # enum crdt_diff_bits: the bits of a crdt_diff_tables flag byte
 DIFF_B_AHEAD = 2
 DIFF_CONFLICT = 4
@@ -86,6 +93,8 @@ TABLE_TILE = 2048                          # rows per workgroup of crdt_merge_ta
 TABLE_CLOCK_GRID = 2048                    # workgroups of its clock pass, striding over the tiles (kTmClockGrid)
 FANIN_MAX = 8                              # sources of one crdt_fanin_tables (include/crdt_merge.h CRDT_FANIN_MAX)
 FANOUT_MAX = 8                             # destinations of one crdt_fanout_tables (CRDT_FANOUT_MAX)
+PURGE_MAX = 8                              # members of one crdt_purge_tombstones (CRDT_PURGE_MAX)
+PURGE_GRID = 2048                          # workgroups of its pass, striding over the tiles (table_purge.inc kPgGrid)
 SYNC_CLOCK_GRID = 2048                     # workgroups of crdt_sync_tables' clock pass (table_merge.inc kSyClockGrid)
 
 # crdt_comm_ops callbacks (include/crdt_merge.h)
@@ -148,6 +157,7 @@ SIGNATURES = {
     "crdt_fanout_tables": (_INT, [_P, _P, _P, _U32, _U64, _I64, _P, _I32, _P]),
     "crdt_diff_tables": (_INT, [_P, _P, _U64, _P, _I32, _P]),
     "crdt_digest_rows": (_INT, [_P, _U64, _U64, _I32, _P, _I32]),
+    "crdt_purge_tombstones": (_INT, [_P, _U32, _U64, _I64, _P, _I32, _P]),
     "crdt_comm_unique_id": (_INT, [_P]),
     "crdt_comm_init_rccl": (_INT, [_P, _U32, _U32, _P]),
     "crdt_comm_init_ops": (_INT, [_P, _U32, _U32, _P]),

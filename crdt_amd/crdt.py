@@ -196,6 +196,8 @@ class MapCrdt(Crdt):
         self.last_sync_winners = None     # winner records it fetched from the device (None: no export ran)
         self.last_diff = None             # "table" | "object": how this map's last diff() ran
         self.last_clear = None            # "table": the last clear() ran on the device table
+        self.last_purge = None            # "table" | "object": how this map's last purgeDeleted() ran
+        self._purged = False              # purgeDeleted() dropped a key here: its id stays, its row is the fill
         self._group.register([nodeId])    # (a shift of ranks reaches the members there are)
         self._table = DeviceTable(device, local_rank=self._nodes.rank(nodeId), capacity=capacity)
         self._table.set_rank_bound(len(self._nodes))
@@ -222,6 +224,11 @@ class MapCrdt(Crdt):
     def _shared(self) -> bool:
         """Whether this map has live siblings (a group of one answers as a plain ``MapCrdt`` always has)."""
         return len(self._group.members()) > 1
+
+    def _sparse(self) -> bool:
+        """Whether an interned key may have no record here: a sibling interned it, or purgeDeleted() dropped
+        it (either way its row holds the never-written fill, ``FILL_LT``)."""
+        return self._purged or self._shared()
 
     def _reserve(self):
         if len(self._keys) > self._table.capacity:
@@ -330,7 +337,7 @@ class MapCrdt(Crdt):
     # ------------------------------------------------------------ SPI
     def containsKey(self, key) -> bool:                                 # map_crdt.dart:21
         kid = self._keys.get(key)
-        if kid is None or not self._shared():
+        if kid is None or not self._sparse():
             return kid is not None
         self._reserve()                                 # (a sibling may have interned the key)
         return int(self._table.read_rows(np.array([kid], np.uint32))[0][0]) != FILL_LT
@@ -339,7 +346,7 @@ class MapCrdt(Crdt):
         kid = self._keys.get(key)
         if kid is None:
             return None
-        shared = self._shared()
+        shared = self._sparse()
         if shared:
             self._reserve()
         lt, rank, val, mod = self._table.read_rows(np.array([kid], np.uint32))
@@ -422,6 +429,7 @@ class MapCrdt(Crdt):
         if not self._shared():                          # (a member clears its own rows and overrides only)
             self._keys.clear()
             self._values.clear()
+            self._purged = False                        # (no key id is left without a record)
         self._hlc_override.clear()
         self._mod_override.clear()
 
@@ -484,6 +492,76 @@ class MapCrdt(Crdt):
                 for k in ids:                           # id order: the order self.map iterates
                     self._emit(keys[k], None)
         self._maybe_compact()
+
+    def purgeDeleted(self, before: Hlc | None = None, replicas=()) -> int:
+        """Tombstone collection: drop the deletions that this map and every one of ``replicas`` hold alike.
+        Let P be the keys k that every map m of ``[self, *replicas]`` holds in ``m.recordMap()`` (a record with a
+        negative ``modified`` is not seen by it, as it is not by ``merge``), each such record ``isDeleted`` and
+        with the Hlc that ``self``'s has, that Hlc's ``logicalTime`` below ``before.logicalTime``
+        (``before=None``: no bound).  Every key of P is removed from the storage of every
+        one of those maps, and ``len(P)`` is returned.  A replica that has not seen the deletion blocks it in
+        all of them: it could still hand the older live record back.  No watch event is emitted, no clock
+        moves, ``last_sync`` is untouched and nothing is interned.
+
+        Between up to ``_capi.PURGE_MAX`` members of one group that keep no Hlc on the host it runs on the
+        device tables (``crdt_purge_tombstones``, ``last_purge == "table"``); the purged ids are fetched
+        (``crdt_export_flagged``) only when a participant keeps a ``modified`` on the host, whose entries of the
+        purged keys are dropped.  Anything else runs the definition on the ``recordMap()``s and clears the rows
+        one by one (``last_purge == "object"``): maps of different groups, an Hlc kept on the host, and more
+        than ``PURGE_MAX`` maps (one call purges what its members agree on at once, so a second chunk could
+        not take back what a ninth map blocks).
+
+        A purged key keeps its key id: a later ``put`` or ``merge`` of it stores it again at its old place in
+        the iteration order (the group's "first seen" order rule), and a map that has purged anything answers
+        ``containsKey`` / ``getRecord`` / ``isDeleted`` / ``get`` through the never-written check that group
+        members use, until ``purge()`` on an unshared map resets it."""
+        maps = [self]
+        for m in replicas:
+            if not any(m is x for x in maps):
+                maps.append(m)
+        if any(m._table.device != self._table.device for m in maps):
+            raise ValueError("replicas of different devices cannot purge together")
+        table = (len(maps) <= _capi.PURGE_MAX and all(m._group is self._group for m in maps)
+                 and not any(m._hlc_override for m in maps))
+        if not table:
+            self.last_purge = "object"
+            return self._purge_objects(maps, before)
+        self.last_purge = "table"
+        n = len(self._keys)
+        for m in maps:
+            m._reserve()
+        keyed = any(m._mod_override for m in maps)
+        before_lt = before.logicalTime if before is not None else (1 << 63) - 1
+        res, flags = self._table.purge_tombstones([m._table for m in maps[1:]], n, before_lt, row_flags=keyed)
+        if res["n_purged"]:
+            if keyed:
+                ids = self._table.export_flagged(n, flags, 1).columns()[0].tolist()
+            for m in maps:
+                m._purged = True
+                if m._mod_override:
+                    for k in ids:
+                        m._mod_override.pop(k, None)
+        return res["n_purged"]
+
+    @staticmethod
+    def _purge_objects(maps, before: Hlc | None) -> int:
+        """The definition itself, on the maps' recordMap()s."""
+        first, rest = maps[0].recordMap(), [m.recordMap() for m in maps[1:]]
+        purged = []
+        for k, r in first.items():
+            if not r.isDeleted or (before is not None and not r.hlc.logicalTime < before.logicalTime):
+                continue
+            others = [rm.get(k) for rm in rest]
+            if all(o is not None and o.isDeleted and o.hlc == r.hlc for o in others):
+                purged.append(k)
+        for m in maps:
+            for k in purged:
+                kid = m._keys.get(k)
+                m._table.clear_rows(kid, 1)
+                m._hlc_override.pop(kid, None)
+                m._mod_override.pop(kid, None)
+            m._purged = m._purged or bool(purged)
+        return len(purged)
 
     # ------------------------------------------------------------ merge
     def _native_ingest(self) -> bool:

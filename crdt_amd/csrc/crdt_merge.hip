@@ -1797,6 +1797,7 @@ __global__ __launch_bounds__(kExThreads) void k_xf_write(Table table, uint64_t n
 #include "table_merge.inc"
 #include "table_diff.inc"
 #include "table_live.inc"
+#include "table_purge.inc"
 
 __global__ __launch_bounds__(256) void k_fill_i64(long long* __restrict__ p, uint64_t n, long long v)
 {
@@ -4976,6 +4977,49 @@ int crdt_digest_rows(crdt_ctx* c, uint64_t n_rows, uint64_t block_rows, int32_t 
     if (mem == CRDT_MEM_HOST)
         HIPCHK(hipMemcpyAsync(out_words, dw, n_words * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
+    return CRDT_OK;
+}
+
+// ---- crdt_purge_tombstones: the tombstones every member holds alike, dropped from all of them (table_purge.inc)
+int crdt_purge_tombstones(crdt_ctx* const* ctxs, uint32_t n_ctx, uint64_t n_rows, int64_t before_lt,
+                          uint8_t* row_flags, int32_t flags_mem, crdt_purge* out) {
+    if (!ctxs || !out || n_ctx == 0 || n_ctx > CRDT_PURGE_MAX) return CRDT_E_INVALID;
+    for (uint32_t j = 0; j < n_ctx; ++j)
+        if (!ctxs[j]) return CRDT_E_INVALID;              // (every null check before a ctx is read)
+    crdt_ctx* c0 = ctxs[0];
+    if (row_flags && flags_mem != CRDT_MEM_HOST && flags_mem != CRDT_MEM_DEVICE) return CRDT_E_INVALID;
+    for (uint32_t j = 0; j < n_ctx; ++j) {
+        const crdt_ctx* c = ctxs[j];
+        if (c->device != c0->device || c->has_comm || n_rows > c->cap) return CRDT_E_INVALID;
+        for (uint32_t k = 0; k < j; ++k)
+            if (ctxs[k] == c) return CRDT_E_INVALID;      // (a row would have two owners)
+    }
+    crdt_purge r = {0, 0};
+    if (n_rows == 0) { *out = r; return CRDT_OK; }
+    HIPCHK(hipSetDevice(c0->device));
+    // every member's rows are final before c0's stream reads and writes them
+    for (uint32_t j = 1; j < n_ctx; ++j) HIPCHK(hipStreamSynchronize(ctxs[j]->stream));
+    uint8_t* rf;
+    int st;
+    if ((st = tm_stage_flags(c0, row_flags, flags_mem, n_rows, &rf))) return st;
+    const uint64_t rows = ex_rows(c0, n_rows, 0);         // (member 0's rows from its high-water mark on are fill)
+    unsigned long long w[2] = {0, 0};
+    if (rows) {
+        PgArgs pa{};
+        for (uint32_t j = 0; j < n_ctx; ++j) pa.t[j] = ctxs[j]->table;
+        unsigned long long* words = reinterpret_cast<unsigned long long*>(c0->d_word.p);
+        HIPCHK(hipMemsetAsync(words, 0, sizeof(w), c0->stream));
+        const unsigned nb = grid_for(rows, kTmTile);
+        k_pg_purge<<<std::min(nb, kPgGrid), kTmThreads, 0, c0->stream>>>(pa, n_ctx, rows, nb, before_lt, rf, words);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(w, words, sizeof(w), hipMemcpyDeviceToHost, c0->stream));
+    }
+    if (rf && n_rows > rows) HIPCHK(hipMemsetAsync(rf + rows, 0, n_rows - rows, c0->stream));
+    if ((st = tm_flags_to_host(c0, row_flags, rf, flags_mem, n_rows))) return st;
+    HIPCHK(hipStreamSynchronize(c0->stream));
+    r.n_candidates = w[0];
+    r.n_purged = w[1];
+    *out = r;
     return CRDT_OK;
 }
 

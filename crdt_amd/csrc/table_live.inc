@@ -23,6 +23,19 @@ __device__ inline unsigned long long lv_spread8(uint32_t b)
     return ((y + 0x7F7F7F7F7F7F7F7Full) >> 7) & 0x0101010101010101ull;   // (a byte is at most 0x80: no carry out)
 }
 
+// One wave-instruction's flag bytes: the 64 consecutive rows from seg on, this lane's row seg + lane carrying
+// bit.  Every lane of the wave calls it (it takes the ballot); shared with k_pg_purge (table_purge.inc).
+__device__ inline void lv_store_flags(uint8_t* __restrict__ flags, uint64_t seg, uint64_t n, int lane, bool bit)
+{
+    const unsigned long long b = __ballot(bit);
+    if (seg + 64 <= n && (reinterpret_cast<uintptr_t>(flags + seg) & 7u) == 0) {
+        if (lane < 8)
+            reinterpret_cast<unsigned long long*>(flags + seg)[lane] = lv_spread8((uint32_t)(b >> (8 * lane)));
+    } else if (seg + lane < n) {
+        flags[seg + lane] = (uint8_t)bit;
+    }
+}
+
 __global__ __launch_bounds__(kTmThreads) void k_lv_tombstone(Table t, uint64_t n, uint32_t nb, int64_t stamp,
                                                              uint32_t local_rank, uint8_t* __restrict__ flags,
                                                              unsigned long long* __restrict__ word)
@@ -48,15 +61,7 @@ __global__ __launch_bounds__(kTmThreads) void k_lv_tombstone(Table t, uint64_t n
             const bool is_live = i < n && (int32_t)v[q].x >= 0 && v[q].z != CRDT_NULL_VALUE;
             if (is_live) store_hc(t, i, th, tx);
             live += is_live;
-            if (!flags) continue;
-            const unsigned long long b = __ballot(is_live);
-            const uint64_t seg = base + (uint64_t)q * kTmThreads + (uint64_t)w * 64;
-            if (seg + 64 <= n && (reinterpret_cast<uintptr_t>(flags + seg) & 7u) == 0) {
-                if (lane < 8)
-                    reinterpret_cast<unsigned long long*>(flags + seg)[lane] = lv_spread8((uint32_t)(b >> (8 * lane)));
-            } else if (seg + lane < n) {
-                flags[seg + lane] = (uint8_t)is_live;
-            }
+            if (flags) lv_store_flags(flags, base + (uint64_t)q * kTmThreads + (uint64_t)w * 64, n, lane, is_live);
         }
     }
 #pragma unroll

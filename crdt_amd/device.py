@@ -466,6 +466,30 @@ class DeviceTable:
             flags_arr = flags_arr[:n_rows]
         return res.as_dict(), flags_arr
 
+    def purge_tombstones(self, others, n_rows: int, before: int, row_flags=False):
+        """Tombstone collection (``crdt_purge_tombstones``) over this table (member 0) and up to
+        ``_capi.PURGE_MAX - 1`` ``others`` of its device and id space; ``others=()`` is one table collecting
+        its own.  A row of [0, n_rows) is a candidate iff this table holds it as a visible tombstone with
+        ``lt < before`` (signed, strict), and purged iff every member holds a visible tombstone of the same
+        (lt, rank); a member that holds the row invisibly blocks it.  A purged row becomes the never-written
+        fill in every member (what ``clear_rows(i, 1)`` writes); nothing else, no canonical and no export view
+        is touched.  Returns ({"n_candidates", "n_purged"}, row flags or None): the flags are indexed by ROW
+        id, one byte for each of ``n_rows`` rows, 1 where the row was purged (they feed ``export_flagged`` on
+        any member).  ``row_flags``: as ``merge_table``'s."""
+        others = list(others)
+        for t in others:
+            if t.device != self.device:
+                raise ValueError(f"purge_tombstones: a member table is on device {t.device}, this one on {self.device}")
+        n_rows, n_ctx = int(n_rows), 1 + len(others)
+        flags_arr, fptr, mem = self._row_flags_arg(row_flags, n_rows)
+        ctxs = (ctypes.c_void_p * n_ctx)(self._ctx.value, *(t._ctx.value for t in others))
+        out = _capi.CrdtPurge()
+        st = self._lib.crdt_purge_tombstones(ctxs, n_ctx, n_rows, int(before), fptr, mem, ctypes.byref(out))
+        self._check(st, "crdt_purge_tombstones")
+        if row_flags is True:
+            flags_arr = flags_arr[:n_rows]
+        return out.as_dict(), flags_arr
+
     def _batch(self, key, lt, rank, val, offsets, millis):
         c = _Cols(self.device, key=(key, "u4"), lt=(lt, "i8"), rank=(rank, "u4"), val=(val, "u4"), millis=(millis, "i8"))
         offs = np.ascontiguousarray(offsets, dtype=np.uint64)

@@ -238,7 +238,9 @@ int crdt_count_since(crdt_ctx* ctx, uint64_t n_rows, int64_t since_lt, uint64_t*
  *       b.merge(a.recordMap()) would store), CRDT_DIFF_B_AHEAD read against b the one a lacks, and
  *       CRDT_DIFF_CONFLICT read against either gives that side's records of the rows no merge can heal.
  *   crdt_tombstone_live(ctx, .., row_flags): read against ctx itself, key_id holds the ids of the watch()
- *       events of that clear(), in id order (every such record is the tombstone {C, local node, null, C}). */
+ *       events of that clear(), in id order (every such record is the tombstone {C, local node, null, C}).
+ *   crdt_purge_tombstones(ctxs, .., row_flags): read against any member, key_id is the list of purged ids, in
+ *       id order (the other columns are the fill the purge left). */
 int crdt_export_flagged(crdt_ctx* ctx, uint64_t n_rows, const uint8_t* flags, int32_t flags_mem,
                         uint8_t bits, crdt_export* out);
 /* purge() (map_crdt.dart:51-52) and rollback of interned-but-uncommitted ids. */
@@ -493,6 +495,40 @@ int crdt_diff_tables(crdt_ctx* a, crdt_ctx* b, uint64_t n_rows, uint8_t* diff_fl
 enum crdt_digest_kind { CRDT_DIGEST_ROWS = 0, CRDT_DIGEST_STATE = 1 };
 int crdt_digest_rows(crdt_ctx* ctx, uint64_t n_rows, uint64_t block_rows, int32_t kind,
                      uint64_t* out_words, int32_t mem /* of out_words */);
+
+/* ---- tombstone collection: drop the deletions a group of replicas agrees on ----
+ * A deletion is a record that is kept "since the deletion needs to be propagated" (crdt.dart:56-58, 64-66); once
+ * every replica holds it, it propagates to nobody.  For 1 <= n_ctx <= CRDT_PURGE_MAX DISTINCT ctxs on the SAME
+ * device sharing one key / node / value interning.  For row i of [0, n_rows) and member j:
+ *     vis_j  = !(mod_j < 0)                        (crdt_tombstone_live's predicates)
+ *     tomb_j = vis_j && val_j == CRDT_NULL_VALUE
+ * Row i is a CANDIDATE iff tomb_0 && lt_0 < before_lt (signed, strict), and PURGED iff it is a candidate and for
+ * every j: tomb_j && lt_j == lt_0 && rank_j == rank_0.  mod is never compared: replicas stamp their own.
+ * A purged row is overwritten in EVERY member with the never-written fill: the bytes crdt_clear_rows(ctx, i, 1)
+ * writes, over the row's whole stride.  Every other row of every member, and every row at or above n_rows, is
+ * untouched.  A member that holds the row invisibly (never written, cleared, above its high-water mark) blocks
+ * the purge: a replica that has not seen the deletion could still be handed the older live record.
+ * For every input the call leaves what this composition leaves:
+ *     crdt_export_since(ctxs[j], n_rows, 0, ..) of every member; the intersection above on the host;
+ *     crdt_clear_rows(ctxs[j], id, 1) for each purged id on every member
+ * except the high-water marks, which the call leaves alone ("rows at or above it hold the fill" stays true).
+ * out->n_candidates counts the candidate rows, out->n_purged the purged ones (the same number on every member).
+ * row_flags (optional, memory of kind flags_mem, any alignment): [n_rows] bytes indexed by ROW id, every entry
+ * written: 1 where the row was purged, else 0.  They feed crdt_export_flagged (its list above).
+ * Untouched: every canonical, every export view, crdt_last_plan, crdt_last_path and crdt_timing.  The call takes
+ * no clock and cannot raise.  n_rows == 0 gives zeros; before_lt == INT64_MIN purges nothing; n_ctx == 1 is one
+ * table collecting its own tombstones.
+ * One streaming pass (table_purge.inc): member 0's table is read once, a later member only at the rows that are
+ * still agreed, and only the purged rows are stored.  Its scratch is two words on ctxs[0] (and, for flags in host
+ * memory, its flag staging): nothing grows with the table.
+ * CRDT_E_INVALID, nothing touched: a null ctxs, out or ctxs[j] (checked before any ctx is read), n_ctx == 0 or
+ * > CRDT_PURGE_MAX, a ctx listed twice, n_rows above any member's capacity, a ctx on another device, a ctx
+ * joined to a communicator, a bad flags_mem with a flags pointer.  No member may be in another call; the work
+ * runs on ctxs[0]'s stream after every other member's stream is drained, and the call is synchronous. */
+#define CRDT_PURGE_MAX 8
+typedef struct crdt_purge { uint64_t n_candidates, n_purged; } crdt_purge;
+int crdt_purge_tombstones(crdt_ctx* const* ctxs, uint32_t n_ctx, uint64_t n_rows, int64_t before_lt,
+                          uint8_t* row_flags, int32_t flags_mem, crdt_purge* out);
 
 /* ---- key-sharded multi-GPU (north star config 4) -------------
  * n_ranks ctxs — one per GPU, normally one process per GPU — form ONE replica whose
