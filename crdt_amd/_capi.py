@@ -78,6 +78,20 @@ class CrdtPurge(ctypes.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+GROUP_MAX = 8                              # members of one crdt_diff_group (include/crdt_merge.h CRDT_GROUP_MAX)
+
+
+class CrdtGroupDiff(ctypes.Structure):
+    _fields_ = [("n_held", ctypes.c_uint64), ("n_disputed", ctypes.c_uint64), ("n_conflict", ctypes.c_uint64),
+                ("first_diff", ctypes.c_uint64), ("n_visible", ctypes.c_uint64 * GROUP_MAX),
+                ("n_behind", ctypes.c_uint64 * GROUP_MAX), ("n_sole", ctypes.c_uint64 * GROUP_MAX)]
+
+    def as_dict(self) -> dict:
+        """The scalar fields as ints, the per-member fields as lists of ``GROUP_MAX`` ints."""
+        return {f: (list(getattr(self, f)) if f in ("n_visible", "n_behind", "n_sole") else getattr(self, f))
+                for f, _ in self._fields_}
+
+
 DIFF_A_AHEAD = 1                           # enum crdt_diff_bits: the bits of a crdt_diff_tables flag byte
 DIFF_B_AHEAD = 2
 DIFF_CONFLICT = 4
@@ -158,6 +172,7 @@ SIGNATURES = {
     "crdt_diff_tables": (_INT, [_P, _P, _U64, _P, _I32, _P]),
     "crdt_digest_rows": (_INT, [_P, _U64, _U64, _I32, _P, _I32]),
     "crdt_purge_tombstones": (_INT, [_P, _U32, _U64, _I64, _P, _I32, _P]),
+    "crdt_diff_group": (_INT, [_P, _U32, _U64, _P, _P, _P, _I32, _P]),
     "crdt_comm_unique_id": (_INT, [_P]),
     "crdt_comm_init_rccl": (_INT, [_P, _U32, _U32, _P]),
     "crdt_comm_init_ops": (_INT, [_P, _U32, _U32, _P]),

@@ -62,6 +62,33 @@ class ReplicaDiff:
         return f"ReplicaDiff(ahead={self.ahead}, behind={self.behind}, conflicts={self.conflicts})"
 
 
+class GroupDiff:
+    """What ``MapCrdt.groupDiff`` found among ``maps = [self, *replicas]``: per map, in ``maps`` order, the number
+    of keys on which it lacks the group's winning record (``behind``) and on which it alone holds it (``sole``:
+    news nobody else has); the number of keys on which some map is behind (``disputed``) and on which two holders
+    of the winning Hlc carry different values (``conflicts``: no merge heals those).  With ``keys=True`` also
+    ``behind_keys[j]`` per map and ``conflict_keys`` (else None)."""
+
+    __slots__ = ("behind", "sole", "disputed", "conflicts", "behind_keys", "conflict_keys")
+
+    def __init__(self, behind, sole, disputed: int, conflicts: int, behind_keys=None, conflict_keys=None):
+        self.behind, self.sole = [int(x) for x in behind], [int(x) for x in sole]
+        self.disputed, self.conflicts = int(disputed), int(conflicts)
+        self.behind_keys, self.conflict_keys = behind_keys, conflict_keys
+
+    @property
+    def converged(self) -> bool:
+        return self.disputed == 0 and self.conflicts == 0
+
+    def __repr__(self):
+        return (f"GroupDiff(behind={self.behind}, sole={self.sole}, disputed={self.disputed}, "
+                f"conflicts={self.conflicts})")
+
+
+def _any_two_differ(values: list) -> bool:
+    return any(a != b for i, a in enumerate(values) for b in values[i + 1:])
+
+
 FILL_LT = -0x7F7F7F7F7F7F7F80     # lt of a never-written row (bytes 0x80: DESIGN.md §2), outside the clock domain
 
 
@@ -194,7 +221,7 @@ class MapCrdt(Crdt):
         self._rank_bound = 0
         self.last_sync = None             # "table" | "object": how the last replica sync into this map ran
         self.last_sync_winners = None     # winner records it fetched from the device (None: no export ran)
-        self.last_diff = None             # "table" | "object": how this map's last diff() ran
+        self.last_diff = None             # "table" | "object": how this map's last diff() / groupDiff() ran
         self.last_clear = None            # "table": the last clear() ran on the device table
         self.last_purge = None            # "table" | "object": how this map's last purgeDeleted() ran
         self._purged = False              # purgeDeleted() dropped a key here: its id stays, its row is the fill
@@ -934,6 +961,89 @@ class MapCrdt(Crdt):
     def convergedWith(self, other: "MapCrdt") -> bool:
         """Whether ``self.recordMap() == other.recordMap()`` under ``Record ==`` (``diff(other).converged``)."""
         return self.diff(other).converged
+
+    # groupDiff() is DEFINED on the recordMap()s of maps = [self, *replicas] (de-duplicated by identity): per key
+    # of their union, the holders are the maps whose record has the greatest Hlc, every other map (one without a
+    # record included) is behind, and the key is a conflict iff two holders' values differ under !=.
+
+    def groupDiff(self, replicas, keys: bool = False) -> GroupDiff:
+        """Where this map and ``replicas`` stand as a group (``GroupDiff``); ``keys=True`` adds the key lists, in
+        the group's key order.  Up to ``_capi.GROUP_MAX`` members of one group that keep no Hlc on the host are
+        compared on the device tables in one pass (``crdt_diff_group``, ``last_diff == "table"``); anything else
+        runs the definition on the ``recordMap()``s (``last_diff == "object"``)."""
+        maps = [self]
+        for m in replicas:
+            if not any(m is x for x in maps):
+                maps.append(m)
+        if any(m._table.device != self._table.device for m in maps):
+            raise ValueError("replicas of different devices cannot be compared")
+        table = (len(maps) <= _capi.GROUP_MAX and all(m._group is self._group for m in maps)
+                 and not any(m._hlc_override for m in maps))
+        if not table:
+            self.last_diff = "object"
+            return self._group_objects(maps, keys)
+        self.last_diff = "table"
+        n, k = len(self._keys), len(maps)
+        for m in maps:
+            m._reserve()
+        others = [m._table for m in maps[1:]]
+        d, behind, hold, conflict = self._table.diff_group(others, n, masks=keys)
+        n_conf, conf_ids = d["n_conflict"], None
+        if n_conf:
+            # the tables compare values by handle, and equal values may sit under two handles: the definition
+            # compares the values of the holders, whose bits the hold bytes of the conflict rows carry
+            if conflict is None:
+                d, behind, hold, conflict = self._table.diff_group(others, n, masks=True)
+            ids = self._table.export_flagged(n, conflict, 1).columns()[0]
+            vals = [m._table.export_flagged(n, conflict, 1).columns()[3].tolist() for m in maps]
+            import torch
+            held = hold[torch.from_numpy(ids.astype(np.int64)).to(hold.device)].cpu().tolist()
+            get = self._values.get
+            real = np.zeros(len(ids), bool)
+            for r, h in enumerate(held):
+                handles = {vals[j][r] for j in range(k) if (h >> j) & 1}
+                real[r] = len(handles) > 1 and _any_two_differ([get(v) for v in handles])
+            conf_ids, n_conf = ids[real], int(real.sum())
+        if not keys:
+            return GroupDiff(d["n_behind"][:k], d["n_sole"][:k], d["n_disputed"], n_conf)
+        names = self._keys.keys
+        behind_keys = [[names[i] for i in self._table.export_flagged(n, behind, 1 << j).columns()[0].tolist()]
+                       if d["n_behind"][j] else [] for j in range(k)]
+        return GroupDiff(d["n_behind"][:k], d["n_sole"][:k], d["n_disputed"], n_conf, behind_keys,
+                         [names[i] for i in conf_ids.tolist()] if n_conf else [])
+
+    def _group_objects(self, maps, keys: bool) -> GroupDiff:
+        """The definition itself, on the maps' recordMap()s."""
+        rms = [m.recordMap() for m in maps]
+        order = list(dict.fromkeys(k for rm in rms for k in rm))
+        if all(m._group is self._group for m in maps):
+            order.sort(key=self._keys.get)
+        k = len(maps)
+        behind, sole, disputed, conflicts = [[] for _ in range(k)], [0] * k, 0, []
+        for key in order:
+            recs = [rm.get(key) for rm in rms]
+            top = None
+            for r in recs:
+                if r is not None and (top is None or r.hlc > top):
+                    top = r.hlc
+            holders = [j for j, r in enumerate(recs) if r is not None and r.hlc == top]
+            for j in range(k):
+                if j not in holders:
+                    behind[j].append(key)
+            disputed += len(holders) < k
+            if len(holders) == 1:
+                sole[holders[0]] += 1
+            if _any_two_differ([recs[j].value for j in holders]):
+                conflicts.append(key)
+        counts = [len(b) for b in behind]
+        if not keys:
+            return GroupDiff(counts, sole, disputed, len(conflicts))
+        return GroupDiff(counts, sole, disputed, len(conflicts), behind, conflicts)
+
+    def convergedAll(self, replicas) -> bool:
+        """Whether every map of ``[self, *replicas]`` has the same ``recordMap()`` under ``Record ==``
+        (``groupDiff(replicas).converged``)."""
+        return self.groupDiff(replicas).converged
 
     def stateDigest(self, block_rows: int = 1 << 20) -> np.ndarray:
         """One uint64 word per ``block_rows`` key ids of what ``recordMap()`` holds under ``Record ==``

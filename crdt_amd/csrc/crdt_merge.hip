@@ -1798,6 +1798,7 @@ __global__ __launch_bounds__(kExThreads) void k_xf_write(Table table, uint64_t n
 #include "table_diff.inc"
 #include "table_live.inc"
 #include "table_purge.inc"
+#include "table_group.inc"
 
 __global__ __launch_bounds__(256) void k_fill_i64(long long* __restrict__ p, uint64_t n, long long v)
 {
@@ -1982,7 +1983,8 @@ struct crdt_ctx {
     DBuf<uint8_t> t_wflags;
     DBuf<uint8_t> t_fstep, t_fmask;    // crdt_fanin_tables' composition: one step's row flags, a host mask's staging
     DBuf<unsigned long long> t_fcounts; // its fused form: the sources' striped n_present / n_won (k_fan_apply)
-    DBuf<unsigned long long> df_words;  // crdt_diff_tables' six words / crdt_digest_rows' words for host memory (table_diff.inc)
+    DBuf<unsigned long long> df_words;  // crdt_diff_tables' six words / crdt_digest_rows' words for host memory (table_diff.inc);
+                                        // crdt_diff_group's 28 (table_group.inc)
     bool table_merge = true;           // CRDT_TABLE_MERGE=0: every crdt_merge_table takes the composition
     bool last_table = false;           // the last merge on this ctx ran the fused table form
     bool last_sync = false;            // ... as one side of a fused crdt_sync_tables
@@ -5019,6 +5021,59 @@ int crdt_purge_tombstones(crdt_ctx* const* ctxs, uint32_t n_ctx, uint64_t n_rows
     HIPCHK(hipStreamSynchronize(c0->stream));
     r.n_candidates = w[0];
     r.n_purged = w[1];
+    *out = r;
+    return CRDT_OK;
+}
+
+// ---- crdt_diff_group: the read-only comparison of up to 8 replicas in one pass (table_group.inc)
+int crdt_diff_group(crdt_ctx* const* ctxs, uint32_t n_ctx, uint64_t n_rows, uint8_t* behind_mask, uint8_t* hold_mask,
+                    uint8_t* conflict_flags, int32_t flags_mem, crdt_group_diff* out) {
+    if (!ctxs || !out || n_ctx == 0 || n_ctx > CRDT_GROUP_MAX) return CRDT_E_INVALID;
+    for (uint32_t j = 0; j < n_ctx; ++j)
+        if (!ctxs[j]) return CRDT_E_INVALID;              // (every null check before a ctx is read)
+    crdt_ctx* c0 = ctxs[0];
+    uint8_t* const host[3] = {behind_mask, hold_mask, conflict_flags};
+    if ((host[0] || host[1] || host[2]) && flags_mem != CRDT_MEM_HOST && flags_mem != CRDT_MEM_DEVICE)
+        return CRDT_E_INVALID;
+    for (uint32_t j = 0; j < n_ctx; ++j) {
+        const crdt_ctx* c = ctxs[j];
+        if (c->device != c0->device || c->has_comm || n_rows > c->cap) return CRDT_E_INVALID;
+        for (uint32_t k = 0; k < j; ++k)
+            if (ctxs[k] == c) return CRDT_E_INVALID;
+    }
+    crdt_group_diff r;
+    memset(&r, 0, sizeof(r));
+    r.first_diff = UINT64_MAX;
+    if (n_rows == 0) { *out = r; return CRDT_OK; }
+    HIPCHK(hipSetDevice(c0->device));
+    // every member's rows are final before c0's stream reads them
+    for (uint32_t j = 1; j < n_ctx; ++j) HIPCHK(hipStreamSynchronize(ctxs[j]->stream));
+    uint8_t* dev[3] = {behind_mask, hold_mask, conflict_flags};
+    if (flags_mem == CRDT_MEM_HOST && (host[0] || host[1] || host[2])) {   // one [n_rows] part per array passed
+        size_t parts = 0;
+        for (int k = 0; k < 3; ++k) parts += host[k] != nullptr;
+        HIPALLOC(c0->s_flags.ensure(parts * n_rows));
+        size_t at = 0;
+        for (int k = 0; k < 3; ++k)
+            if (host[k]) { dev[k] = c0->s_flags.p + at; at += n_rows; }
+    }
+    HIPALLOC(c0->df_words.ensure(kGdWords));
+    unsigned long long* words = c0->df_words.p;
+    HIPCHK(hipMemsetAsync(words, 0, kGdWords * sizeof(unsigned long long), c0->stream));
+    HIPCHK(hipMemsetAsync(words + 3, 0xFF, sizeof(unsigned long long), c0->stream));
+    GdArgs ga{};
+    for (uint32_t j = 0; j < n_ctx; ++j) ga.t[j] = ctxs[j]->table;
+    const unsigned nb = grid_for(n_rows, kTmTile);
+    k_gd_diff<<<std::min(nb, kDfGrid), kTmThreads, 0, c0->stream>>>(ga, n_ctx, n_rows, nb, dev[0], dev[1], dev[2], words);
+    HIPCHK(hipGetLastError());
+    for (int k = 0; k < 3; ++k) {
+        int st;
+        if ((st = tm_flags_to_host(c0, host[k], dev[k], flags_mem, n_rows))) return st;
+    }
+    unsigned long long w[kGdWords];
+    HIPCHK(hipMemcpyAsync(w, words, sizeof(w), hipMemcpyDeviceToHost, c0->stream));
+    HIPCHK(hipStreamSynchronize(c0->stream));
+    memcpy(&r, w, sizeof(r));                             // (the words are the struct's fields, in order)
     *out = r;
     return CRDT_OK;
 }

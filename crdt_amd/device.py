@@ -490,6 +490,38 @@ class DeviceTable:
             flags_arr = flags_arr[:n_rows]
         return out.as_dict(), flags_arr
 
+    def diff_group(self, others, n_rows: int, masks=False):
+        """The read-only comparison of this table (member 0) and up to ``_capi.GROUP_MAX - 1`` ``others`` of its
+        device and id space over rows [0, n_rows) (``crdt_diff_group``), every table read once and none written;
+        ``others=()`` is one table on its own.  Per row, with a member visible iff its ``mod >= 0``: ``hold`` has
+        bit j set where member j holds the greatest (lt, rank) among the visible members, ``behind`` bit j where
+        some member holds the row and j's hold bit is clear, ``conflict`` is 1 where two holders carry different
+        value handles; a row nobody holds has three zero bytes.  Returns (dict, behind, hold, conflict): the dict
+        has ``n_held, n_disputed, n_conflict, first_diff`` and the lists ``n_visible, n_behind, n_sole`` of
+        ``GROUP_MAX`` entries (zero from the member count on); the arrays hold one byte per ROW id and feed
+        ``export_flagged``.  ``masks``: False/None -> no array (three ``None``); True -> three torch uint8 tensors
+        on the table's device; a triple (behind, hold, conflict) whose entries are each as ``merge_table``'s
+        ``row_flags``, the arrays that are passed all in one memory (host or device)."""
+        others = list(others)
+        for t in others:
+            if t.device != self.device:
+                raise ValueError(f"diff_group: a member table is on device {t.device}, this one on {self.device}")
+        n_rows, n_ctx = int(n_rows), 1 + len(others)
+        want = tuple(masks) if isinstance(masks, (tuple, list)) else (masks,) * 3
+        if len(want) != 3:
+            raise ValueError("diff_group: masks is True, False or a triple (behind, hold, conflict)")
+        args = [self._row_flags_arg(m, n_rows) for m in want]
+        mems = {mem for _, ptr, mem in args if ptr is not None}
+        if len(mems) > 1:
+            raise ValueError("diff_group: the mask arrays must live in the same memory (host or device)")
+        mem = mems.pop() if mems else _capi.CRDT_MEM_DEVICE
+        ctxs = (ctypes.c_void_p * n_ctx)(self._ctx.value, *(t._ctx.value for t in others))
+        out = _capi.CrdtGroupDiff()
+        st = self._lib.crdt_diff_group(ctxs, n_ctx, n_rows, args[0][1], args[1][1], args[2][1], mem, ctypes.byref(out))
+        self._check(st, "crdt_diff_group")
+        arrs = [(arr[:n_rows] if m is True else arr) for m, (arr, _, _) in zip(want, args)]
+        return out.as_dict(), arrs[0], arrs[1], arrs[2]
+
     def _batch(self, key, lt, rank, val, offsets, millis):
         c = _Cols(self.device, key=(key, "u4"), lt=(lt, "i8"), rank=(rank, "u4"), val=(val, "u4"), millis=(millis, "i8"))
         offs = np.ascontiguousarray(offsets, dtype=np.uint64)

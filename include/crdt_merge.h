@@ -240,7 +240,13 @@ int crdt_count_since(crdt_ctx* ctx, uint64_t n_rows, int64_t since_lt, uint64_t*
  *   crdt_tombstone_live(ctx, .., row_flags): read against ctx itself, key_id holds the ids of the watch()
  *       events of that clear(), in id order (every such record is the tombstone {C, local node, null, C}).
  *   crdt_purge_tombstones(ctxs, .., row_flags): read against any member, key_id is the list of purged ids, in
- *       id order (the other columns are the fill the purge left). */
+ *       id order (the other columns are the fill the purge left).
+ *   crdt_diff_group(ctxs, .., behind_mask, hold_mask, conflict_flags): behind_mask with bits = 1 << j, read against
+ *       any member: key_id lists the keys on which member j is behind, in id order (the other columns belong to
+ *       the member the export was read from and mean nothing here, as after the purge).  hold_mask with
+ *       bits = 1 << h, read against member h: the records on which h holds the group's winner (what a member
+ *       whose behind bit is set there lacks).  conflict_flags, read against a member: that member's records on
+ *       the rows in conflict, the same ids in the same order on every member. */
 int crdt_export_flagged(crdt_ctx* ctx, uint64_t n_rows, const uint8_t* flags, int32_t flags_mem,
                         uint8_t bits, crdt_export* out);
 /* purge() (map_crdt.dart:51-52) and rollback of interned-but-uncommitted ids. */
@@ -529,6 +535,55 @@ int crdt_digest_rows(crdt_ctx* ctx, uint64_t n_rows, uint64_t block_rows, int32_
 typedef struct crdt_purge { uint64_t n_candidates, n_purged; } crdt_purge;
 int crdt_purge_tombstones(crdt_ctx* const* ctxs, uint32_t n_ctx, uint64_t n_rows, int64_t before_lt,
                           uint8_t* row_flags, int32_t flags_mem, crdt_purge* out);
+
+/* ---- read-only comparison of a group of replicas: "are they all converged, who lacks the winning record, who
+ * holds news nobody else has?" ----
+ * For 1 <= n_ctx <= CRDT_GROUP_MAX DISTINCT ctxs on the SAME device sharing one key / node / value interning.  The
+ * predicates are crdt_diff_tables': vis_j = (mod_j >= 0); hlc = (lt, rank), signed lt first, then unsigned rank;
+ * mod is never compared (replicas stamp their own); values are compared by handle.  For row i of [0, n_rows):
+ *     W        = { j : vis_j }.  W empty: all three bytes are 0 and the row's contents are not compared.
+ *     top      = the greatest hlc over W
+ *     hold     bit j set iff j is in W and hlc_j == top
+ *     behind   bit j set iff j < n_ctx and bit j of hold is clear: "not visible" and "visible but lower" alike
+ *     conflict = 1 iff two members whose bits are set in hold have different val (members below the top take no
+ *                part: a conflict between two members that a third overrules with a higher hlc is none)
+ * so hold & behind == 0, and hold | behind == (1 << n_ctx) - 1 wherever W is not empty.
+ * behind_mask, hold_mask, conflict_flags (each optional, all of the memory kind flags_mem, any alignment): [n_rows]
+ * bytes indexed by ROW id, every entry of an array that is passed written.  They feed crdt_export_flagged (its list
+ * above).  *out: n_held counts the rows with W not empty, n_disputed those with a non-zero behind byte, n_conflict
+ * those with conflict == 1, first_diff is the smallest row id that is disputed or in conflict (UINT64_MAX: none);
+ * per member j < n_ctx, n_visible[j] counts its rows with mod >= 0, n_behind[j] the rows carrying its behind bit,
+ * n_sole[j] the rows whose hold byte is exactly 1 << j (news nobody else has).  Entries at or above n_ctx are 0.
+ * Identities:
+ *   n_ctx == 2, ctxs = {a, b}: behind bit 1 is crdt_diff_tables(a, b)'s CRDT_DIFF_A_AHEAD, behind bit 0 its
+ *       CRDT_DIFF_B_AHEAD, conflict its CRDT_DIFF_CONFLICT; first_diff, n_visible[0] and n_visible[1] are its
+ *       first_diff, n_visible_a and n_visible_b.
+ *   n_ctx == 1: behind and conflict are 0 and hold is vis.
+ *   n_disputed == 0 && n_conflict == 0: every member has the same CRDT_DIGEST_STATE words (crdt_digest_rows).
+ *   wherever bit h of hold is set, crdt_diff_tables(ctxs[h], ctxs[j]) has CRDT_DIFF_A_AHEAD set iff bit j of
+ *       behind is set.
+ * Untouched: every table's rows, canonical, high-water mark and export view, crdt_last_plan, crdt_last_path and
+ * crdt_timing.  The call takes no clock and cannot raise.  n_rows == 0 gives zeros with first_diff = UINT64_MAX.
+ * One streaming pass (table_group.inc): every row of every member is read exactly once, no table is written.  Its
+ * scratch is the 28 result words on ctxs[0] (and, for arrays in host memory, its flag staging, one [n_rows] part
+ * per array that is passed): nothing else grows with the table.
+ * CRDT_E_INVALID, nothing touched: a null ctxs, out or ctxs[j] (checked before any ctx is read), n_ctx == 0 or
+ * > CRDT_GROUP_MAX, a ctx listed twice, n_rows above any member's capacity, a ctx on another device, a ctx
+ * joined to a communicator, a bad flags_mem with any array pointer.  No member may be in another call; the work
+ * runs on ctxs[0]'s stream after every other member's stream is drained, and the call is synchronous. */
+#define CRDT_GROUP_MAX 8
+typedef struct crdt_group_diff {
+    uint64_t n_held;        /* rows some member holds visibly */
+    uint64_t n_disputed;    /* rows with a non-zero behind byte */
+    uint64_t n_conflict;    /* rows with conflict == 1 */
+    uint64_t first_diff;    /* smallest row id that is disputed or in conflict; UINT64_MAX: none */
+    uint64_t n_visible[CRDT_GROUP_MAX];  /* per member: rows with mod >= 0 */
+    uint64_t n_behind[CRDT_GROUP_MAX];   /* per member: rows carrying its behind bit */
+    uint64_t n_sole[CRDT_GROUP_MAX];     /* per member: rows whose hold byte is exactly its bit */
+} crdt_group_diff;
+int crdt_diff_group(crdt_ctx* const* ctxs, uint32_t n_ctx, uint64_t n_rows,
+                    uint8_t* behind_mask, uint8_t* hold_mask, uint8_t* conflict_flags,
+                    int32_t flags_mem, crdt_group_diff* out);
 
 /* ---- key-sharded multi-GPU (north star config 4) -------------
  * n_ranks ctxs — one per GPU, normally one process per GPU — form ONE replica whose
