@@ -542,14 +542,7 @@ class MapCrdt(Crdt):
         the iteration order (the group's "first seen" order rule), and a map that has purged anything answers
         ``containsKey`` / ``getRecord`` / ``isDeleted`` / ``get`` through the never-written check that group
         members use, until ``purge()`` on an unshared map resets it."""
-        maps = [self]
-        for m in replicas:
-            if not any(m is x for x in maps):
-                maps.append(m)
-        if any(m._table.device != self._table.device for m in maps):
-            raise ValueError("replicas of different devices cannot purge together")
-        table = (len(maps) <= _capi.PURGE_MAX and all(m._group is self._group for m in maps)
-                 and not any(m._hlc_override for m in maps))
+        maps, table = self._members(replicas, _capi.PURGE_MAX, "purge together")
         if not table:
             self.last_purge = "object"
             return self._purge_objects(maps, before)
@@ -569,6 +562,19 @@ class MapCrdt(Crdt):
                     for k in ids:
                         m._mod_override.pop(k, None)
         return res["n_purged"]
+
+    def _members(self, replicas, limit: int, cannot: str):
+        """``[self, *replicas]`` de-duplicated by identity, and whether an operation over them runs on the device
+        tables: at most ``limit`` members, all of one group, none keeping an Hlc on the host.  ``cannot``: what
+        replicas of different devices are refused with."""
+        maps = [self]
+        for m in replicas:
+            if not any(m is x for x in maps):
+                maps.append(m)
+        if any(m._table.device != self._table.device for m in maps):
+            raise ValueError(f"replicas of different devices cannot {cannot}")
+        return maps, (len(maps) <= limit and all(m._group is self._group for m in maps)
+                      and not any(m._hlc_override for m in maps))
 
     @staticmethod
     def _purge_objects(maps, before: Hlc | None) -> int:
@@ -763,6 +769,14 @@ class MapCrdt(Crdt):
     def _since_lt(h: Hlc | None) -> int:
         return h.logicalTime if h is not None else 0
 
+    @staticmethod
+    def _sinces_for(sinces, replicas, method: str, noun: str) -> list:
+        """One ``modifiedSince`` per replica (None: none for any), or ValueError."""
+        sinces = [None] * len(replicas) if sinces is None else list(sinces)
+        if len(sinces) != len(replicas):
+            raise ValueError(f"{method}: {len(replicas)} {noun} but {len(sinces)} sinces")
+        return sinces
+
     def _table_route(self, sources, others=()) -> bool:
         """Whether a sync among self, ``sources`` and ``others`` runs on the device tables."""
         everyone = [self, *sources, *others]
@@ -845,9 +859,7 @@ class MapCrdt(Crdt):
         that raises."""
         wall = self._wall(wall)
         srcs = list(srcs)
-        sinces = [None] * len(srcs) if sinces is None else list(sinces)
-        if len(sinces) != len(srcs):
-            raise ValueError(f"mergeFromAll: {len(srcs)} sources but {len(sinces)} sinces")
+        sinces = self._sinces_for(sinces, srcs, "mergeFromAll", "sources")
         if not self._table_route(srcs):
             self.last_sync, self.last_sync_winners = "object", None
             for s, t in zip(srcs, sinces):
@@ -873,9 +885,7 @@ class MapCrdt(Crdt):
         that raises."""
         wall = self._wall(wall)
         dsts = list(dsts)
-        sinces = [None] * len(dsts) if sinces is None else list(sinces)
-        if len(sinces) != len(dsts):
-            raise ValueError(f"broadcastTo: {len(dsts)} destinations but {len(sinces)} sinces")
+        sinces = self._sinces_for(sinces, dsts, "broadcastTo", "destinations")
         if not self._table_route([self], dsts):
             for d, t in zip(dsts, sinces):
                 d.last_sync, d.last_sync_winners = "object", None
@@ -971,14 +981,7 @@ class MapCrdt(Crdt):
         the group's key order.  Up to ``_capi.GROUP_MAX`` members of one group that keep no Hlc on the host are
         compared on the device tables in one pass (``crdt_diff_group``, ``last_diff == "table"``); anything else
         runs the definition on the ``recordMap()``s (``last_diff == "object"``)."""
-        maps = [self]
-        for m in replicas:
-            if not any(m is x for x in maps):
-                maps.append(m)
-        if any(m._table.device != self._table.device for m in maps):
-            raise ValueError("replicas of different devices cannot be compared")
-        table = (len(maps) <= _capi.GROUP_MAX and all(m._group is self._group for m in maps)
-                 and not any(m._hlc_override for m in maps))
+        maps, table = self._members(replicas, _capi.GROUP_MAX, "be compared")
         if not table:
             self.last_diff = "object"
             return self._group_objects(maps, keys)

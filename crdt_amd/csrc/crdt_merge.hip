@@ -1986,10 +1986,10 @@ struct crdt_ctx {
     DBuf<unsigned long long> df_words;  // crdt_diff_tables' six words / crdt_digest_rows' words for host memory (table_diff.inc);
                                         // crdt_diff_group's 28 (table_group.inc)
     bool table_merge = true;           // CRDT_TABLE_MERGE=0: every crdt_merge_table takes the composition
-    bool last_table = false;           // the last merge on this ctx ran the fused table form
-    bool last_sync = false;            // ... as one side of a fused crdt_sync_tables
-    bool last_fanin = false;           // ... as the destination of a fused crdt_fanin_tables
-    bool last_fanout = false;          // ... as a destination of a fused crdt_fanout_tables
+    // the last merge on this ctx, if it ran a fused table form: CRDT_PLAN_TABLE, with CRDT_PLAN_SYNC as one
+    // side of crdt_sync_tables, CRDT_PLAN_FANIN as the destination of crdt_fanin_tables, CRDT_PLAN_FANOUT as
+    // a destination of crdt_fanout_tables; else 0
+    uint32_t last_table_plan = 0;
     DBuf<long long> d_word;
     DBuf<unsigned long long> d_ibase;
     // per-call plan (set by scan, used by later phases)
@@ -3944,58 +3944,6 @@ int crdt_put_stamped(crdt_ctx* c, const uint32_t* key_id, const uint32_t* val, u
     return CRDT_OK;
 }
 
-// ---- crdt_tombstone_live: Crdt.clear() (crdt.dart:67-73) on the table (table_live.inc).  What
-// crdt_export_since at 0, a filter on val and crdt_put_stamped of the live ids leave, in one pass: Hlc.send is
-// taken first, the pass stores its stamp over the live rows, and the canonical moves only if there was one
-// (no live row: nothing was written, the no-op of crdt.dart:48).  A send that raises stores nothing: whether
-// it is reported depends on a live row alone, so the count pass answers it.
-static int tm_stage_flags(crdt_ctx* c, uint8_t* flags, int32_t flags_mem, uint64_t n_rows, uint8_t** dev);
-static int tm_flags_to_host(crdt_ctx* c, uint8_t* flags, const uint8_t* dev, int32_t flags_mem, uint64_t n_rows);
-static uint64_t ex_rows(const crdt_ctx* c, uint64_t n_rows, int64_t since);
-
-int crdt_tombstone_live(crdt_ctx* c, uint64_t n_rows, int64_t wall, uint8_t* row_flags, int32_t flags_mem,
-                        crdt_result* out) {
-    if (!c || !out || n_rows > c->cap || c->has_comm ||
-        (row_flags && flags_mem != CRDT_MEM_HOST && flags_mem != CRDT_MEM_DEVICE))
-        return CRDT_E_INVALID;
-    crdt_result res = cleared_result(c->canonical);
-    HIPCHK(hipSetDevice(c->device));
-    uint8_t* rf;
-    int st;
-    if ((st = tm_stage_flags(c, row_flags, flags_mem, n_rows, &rf))) return st;
-    const uint64_t rows = ex_rows(c, n_rows, 0);      // (the rows from the high-water mark on are fill: not live)
-    const HlcSend send = hlc_send(c->canonical, wall);
-    unsigned long long live = 0;
-    if (send.status != CRDT_OK) {
-        uint64_t n_sel = 0, n_live = 0;
-        if ((st = crdt_count_since(c, n_rows, 0, &n_sel, &n_live))) return st;
-        live = n_live;
-        if (rf && n_rows) HIPCHK(hipMemsetAsync(rf, 0, n_rows, c->stream));
-    } else {
-        unsigned long long* word = reinterpret_cast<unsigned long long*>(c->d_word.p);
-        if (rows) {
-            HIPCHK(hipMemsetAsync(word, 0, sizeof(*word), c->stream));
-            const unsigned nb = grid_for(rows, kTmTile);
-            k_lv_tombstone<<<std::min(nb, kLvGrid), kTmThreads, 0, c->stream>>>(c->table, rows, nb, send.canonical,
-                                                                                c->local_rank, rf, word);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipMemcpyAsync(&live, word, sizeof(live), hipMemcpyDeviceToHost, c->stream));
-        }
-        if (rf && n_rows > rows) HIPCHK(hipMemsetAsync(rf + rows, 0, n_rows - rows, c->stream));
-    }
-    if ((st = tm_flags_to_host(c, row_flags, rf, flags_mem, n_rows))) return st;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (live && send.status != CRDT_OK) {
-        send.into(res);
-    } else if (live) {
-        c->canonical = send.canonical;
-        res.canonical_lt = send.canonical;
-        res.n_won = live;
-    }
-    *out = res;
-    return res.status;
-}
-
 int crdt_read_rows(crdt_ctx* c, const uint32_t* key_id, uint64_t n, int64_t* lt, uint32_t* rank,
                    uint32_t* val, int64_t* mod, int32_t mem) {
     if (!c) return CRDT_E_INVALID;
@@ -4291,10 +4239,7 @@ int crdt_merge(crdt_ctx* c, const crdt_batch* batch, int64_t wall, uint8_t* win_
     }
     HIPCHK(hipSetDevice(c->device));
     if (c->env_dynamic) read_env_knobs(c);
-    c->last_table = false;
-    c->last_sync = false;
-    c->last_fanin = false;
-    c->last_fanout = false;
+    c->last_table_plan = 0;
     // rows >= hw_read are read as the fill by this merge; afterwards hw moves to hw_next (the
     // capacity unless finish_apply learned the batch's key bound) on every return path
     c->hw_read = (c->form_off & kFormNoHw) ? c->cap : c->hw;
@@ -4408,10 +4353,34 @@ static int tm_read_words(crdt_ctx* c, unsigned long long* w, int dirs) {
     return CRDT_OK;
 }
 
-// The canonical that the recv loop over one direction's selection leaves (crdt.dart:82): max(C, its largest
-// lt).  w: that direction's clock words.
-static int64_t tm_recv_canonical(int64_t c, const unsigned long long* w) {
-    return w[3] ? imax(c, (int64_t)(w[0] ^ (1ull << 63))) : c;
+// One direction's kTmWords clock words, as the clock pass publishes them (TmClock::publish, table_merge.inc).
+static int64_t tm_w_max_lt(const unsigned long long* w) { return (int64_t)(w[0] ^ (1ull << 63)); }  // (stored biased)
+static uint64_t tm_w_id_end(const unsigned long long* w) { return w[1]; }      // 1 + the largest selected id
+static bool tm_w_may_raise(const unsigned long long* w) { return w[2] != 0; }  // a selected row may raise in recv()
+static uint64_t tm_w_selected(const unsigned long long* w) { return w[3]; }    // selected rows
+
+// What the host decides for one direction between the passes, from its clock words w and the canonical c_in
+// that its receiving ctx enters with.  The recv loop over the selection leaves stamp = max(c_in, its largest
+// lt) (crdt.dart:82); the rows are stored with mod = stamp, then Hlc.send(stamp) (crdt.dart:93) fixes the
+// canonical or raises after the store: res is that outcome, with nothing counted yet.
+struct TmDir {
+    int64_t stamp;
+    crdt_result res;
+    uint64_t id_end;           // where the receiver's high-water mark rises to (0: no row is selected)
+    bool has;                  // a row is selected
+    bool needs_composition;    // a selected row may raise in recv(), or lies outside the receiver (recv_cap rows)
+};
+
+static TmDir tm_direction(int64_t c_in, const unsigned long long* w, uint64_t recv_cap, int64_t wall) {
+    TmDir d;
+    d.has = tm_w_selected(w) != 0;
+    d.id_end = d.has ? tm_w_id_end(w) : 0;
+    d.needs_composition = tm_w_may_raise(w) || d.id_end > recv_cap;
+    d.stamp = d.has ? imax(c_in, tm_w_max_lt(w)) : c_in;
+    d.res = cleared_result(c_in);
+    d.res.n_stored = 1;
+    hlc_send(d.stamp, wall).into(d.res);
+    return d;
 }
 
 // The apply pass writes the flag of every row it covers, [0, covered); the host zeroes the rest.
@@ -4443,21 +4412,71 @@ static int tm_read_misc(crdt_ctx* c) {
 }
 
 // One direction's end: its counts from the striped slots [first, first + count), and on its receiving ctx
-// the high-water mark (every row written is a selected one; w: the direction's clock words), the new
-// canonical and what crdt_last_plan reports.
-static void tm_finish(crdt_ctx* c, crdt_result* res, const Misc* m, int first, int count,
-                      const unsigned long long* w, bool sync) {
+// the high-water mark (every row written is a selected one), the new canonical and what crdt_last_plan
+// reports (plan: CRDT_PLAN_SYNC as one side of a sync, else 0; the fan forms add their own bit).
+static void tm_finish(crdt_ctx* c, TmDir* d, const Misc* m, int first, int count, uint32_t plan) {
     for (int s = first; s < first + count; ++s) {
-        res->n_present += m->present[s];
-        res->n_won += m->won[s];
+        d->res.n_present += m->present[s];
+        d->res.n_won += m->won[s];
     }
-    if (w[3]) raise_hw(c, w[1]);
-    c->canonical = res->canonical_lt;
-    c->last_table = true;
-    c->last_sync = sync;
-    c->last_fanin = false;
-    c->last_fanout = false;
+    raise_hw(c, d->id_end);
+    c->canonical = d->res.canonical_lt;
+    c->last_table_plan = CRDT_PLAN_TABLE | plan;
     c->last_sorted = false;
+}
+
+// The fused fan forms count per direction in t_fcounts (2 * kCounterSlots striped words each: present, then
+// won), not in Misc.  Before pass 2: the words zeroed.
+static int tm_fan_counts_begin(crdt_ctx* c) {
+    HIPALLOC(c->t_fcounts.ensure(kFanCounts));
+    HIPCHK(hipMemsetAsync(c->t_fcounts.p, 0, kFanCounts * sizeof(unsigned long long), c->stream));
+    return CRDT_OK;
+}
+
+// After pass 2: everything queued on the stream done, and each of the n directions' sums in its result.
+static int tm_fan_counts_end(crdt_ctx* c, TmDir* d, uint32_t n) {
+    std::vector<unsigned long long> counts(kFanCounts);
+    HIPCHK(hipMemcpyAsync(counts.data(), c->t_fcounts.p, kFanCounts * sizeof(unsigned long long),
+                          hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    for (uint32_t j = 0; j < n; ++j) {
+        const unsigned long long* cj = counts.data() + 2 * j * kCounterSlots;
+        for (int s = 0; s < kCounterSlots; ++s) {
+            d[j].res.n_present += cj[s];
+            d[j].res.n_won += cj[kCounterSlots + s];
+        }
+    }
+    return CRDT_OK;
+}
+
+// A list of n ctxs that a call takes: the list there, 1 <= n <= max, and no member null (checked before any
+// ctx is read).
+static bool tm_list_ok(crdt_ctx* const* ctxs, uint32_t n, uint32_t max) {
+    if (!ctxs || n == 0 || n > max) return false;
+    for (uint32_t j = 0; j < n; ++j)
+        if (!ctxs[j]) return false;
+    return true;
+}
+
+// ... and as the members of a group operation over n_rows rows: all on member 0's device, none with a
+// communicator, n_rows within each one's capacity, and (distinct) none twice: a row would have two owners.
+static bool tm_members_ok(crdt_ctx* const* ctxs, uint32_t n, uint32_t max, uint64_t n_rows, bool distinct) {
+    if (!tm_list_ok(ctxs, n, max)) return false;
+    for (uint32_t j = 0; j < n; ++j) {
+        const crdt_ctx* c = ctxs[j];
+        if (c->device != ctxs[0]->device || c->has_comm || n_rows > c->cap) return false;
+        for (uint32_t k = 0; distinct && k < j; ++k)
+            if (ctxs[k] == c) return false;
+    }
+    return true;
+}
+
+// Every listed ctx's queued work done, but for c, on whose stream the call runs: the others' rows are final
+// before c's stream reads or writes them.
+static int tm_sync_others(crdt_ctx* c, crdt_ctx* const* ctxs, uint32_t n) {
+    for (uint32_t j = 0; j < n; ++j)
+        if (ctxs[j] != c) HIPCHK(hipStreamSynchronize(ctxs[j]->stream));
+    return CRDT_OK;
 }
 
 // ---- crdt_merge_table: dst.merge(src.recordMap(modifiedSince)) over two aligned tables (table_merge.inc)
@@ -4536,34 +4555,28 @@ int crdt_merge_table(crdt_ctx* dst, crdt_ctx* src, uint64_t n_rows, int64_t sinc
     }
     unsigned long long w[kTmWords] = {};
     if ((st = tm_read_words(dst, w, 1))) return st;
-    const bool has = w[3] != 0;
+    TmDir d = tm_direction(c0, w, dst->cap, wall);
     // a selected row may raise in recv(), or lies outside dst: nothing is written yet, the composition
     // gives the exact stop point, exception details and error
-    if (w[2] || (has && w[1] > dst->cap))
+    if (d.needs_composition)
         return table_merge_composed(dst, src, n_rows, since_lt, wall, row_flags, flags_mem, out);
-    // the recv loop leaves R; the rows are stored with mod = R, then Hlc.send(R) (crdt.dart:93) fixes the
-    // canonical or raises after the store
-    const int64_t R = tm_recv_canonical(c0, w);
-    crdt_result res = cleared_result(c0);
-    res.n_stored = 1;
-    hlc_send(R, wall).into(res);
     ev_record(dst, kEvClock);
-    // pass 2: the winners into dst
+    // pass 2: the winners into dst, stored with mod = R; a send() that raises does so after the store
     if ((st = reset_misc(dst))) return st;
-    if ((st = tm_zero_uncovered(dst, rf, has ? rows : 0, n_rows))) return st;
-    tm_apply_begin(dst, has);
-    if (has) {
+    if ((st = tm_zero_uncovered(dst, rf, d.has ? rows : 0, n_rows))) return st;
+    tm_apply_begin(dst, d.has);
+    if (d.has) {
         k_tm_apply<<<nb, kTmThreads, 0, dst->stream>>>(src->table, dst->table, rows, dst->cap, dst->t_sel.p,
-                                                       dst->t_mask.p, R, dst->d_misc, rf);
+                                                       dst->t_mask.p, d.stamp, dst->d_misc, rf);
         HIPCHK(hipGetLastError());
     }
-    tm_apply_end(dst, has);
+    tm_apply_end(dst, d.has);
     if ((st = tm_flags_to_host(dst, row_flags, rf, flags_mem, n_rows))) return st;
     if ((st = tm_read_misc(dst))) return st;
-    tm_finish(dst, &res, dst->h_misc, 0, kCounterSlots, w, false);
+    tm_finish(dst, &d, dst->h_misc, 0, kCounterSlots, 0);
     collect_timing(dst);
-    *out = res;
-    return res.status;
+    *out = d.res;
+    return d.res.status;
 }
 
 // ---- crdt_sync_tables: a.merge(b.recordMap(since_b)), then b.merge(a.recordMap(since_a)) (table_merge.inc)
@@ -4618,103 +4631,111 @@ int crdt_sync_tables(crdt_ctx* a, crdt_ctx* b, uint64_t n_rows, int64_t since_a,
     unsigned long long w[kSyWords] = {};
     if ((st = tm_read_words(a, w, 2))) return st;
     // the recv loops leave R_a = max(C_a, M_b) and R_b = max(C_b, M_a'); each side's Hlc.send follows its store
-    const int64_t Ra = tm_recv_canonical(ca, w), Rb = tm_recv_canonical(cb, w + kTmWords);
-    crdt_result ra = cleared_result(ca), rb = cleared_result(cb);
-    ra.n_stored = rb.n_stored = 1;
-    hlc_send(Ra, wall).into(ra);
-    hlc_send(Rb, wall).into(rb);
+    // (the capacity part of needs_composition never holds here: n_rows <= cap was checked for both sides)
+    TmDir da = tm_direction(ca, w, a->cap, wall), db = tm_direction(cb, w + kTmWords, b->cap, wall);
     // a row may raise in either recv(), step 1's send() raises (the exchange ends there), or step 1's
     // winners, stamped mod = R_a, would not be selected by since_a (direction 2's words assumed they are):
     // nothing is written yet, the composition gives the exact stop points and exception details
-    if (w[2] || w[kTmWords + 2] || ra.status != CRDT_OK || Ra < since_a)
+    if (da.needs_composition || db.needs_composition || da.res.status != CRDT_OK || da.stamp < since_a)
         return sync_tables_composed(a, b, n_rows, since_a, since_b, wall, flags_a, flags_b, flags_mem, out_a, out_b);
     ev_record(a, kEvClock);
     // pass 2: the winners into both tables (step 2's send() raising after its store stays in place)
     if ((st = reset_misc(a))) return st;
-    const bool has = w[3] || w[kTmWords + 3];         // rows selected in either direction
+    const bool has = da.has || db.has;                // rows selected in either direction
     if ((st = tm_zero_uncovered(a, rfa, has ? rows : 0, n_rows))) return st;
     if ((st = tm_zero_uncovered(a, rfb, has ? rows : 0, n_rows))) return st;
     tm_apply_begin(a, has);
     if (has) {
-        k_sy_apply<<<nb, kTmThreads, 0, a->stream>>>(a->table, b->table, rows, a->t_sel.p, a->t_mask.p, Ra, Rb,
-                                                     a->d_misc, rfa, rfb);
+        k_sy_apply<<<nb, kTmThreads, 0, a->stream>>>(a->table, b->table, rows, a->t_sel.p, a->t_mask.p, da.stamp,
+                                                     db.stamp, a->d_misc, rfa, rfb);
         HIPCHK(hipGetLastError());
     }
     tm_apply_end(a, has);
     if ((st = tm_flags_to_host(a, flags_a, rfa, flags_mem, n_rows))) return st;
     if ((st = tm_flags_to_host(a, flags_b, rfb, flags_mem, n_rows))) return st;
     if ((st = tm_read_misc(a))) return st;
-    tm_finish(a, &ra, a->h_misc, 0, kCounterSlots / 2, w, true);
-    tm_finish(b, &rb, a->h_misc, kCounterSlots / 2, kCounterSlots / 2, w + kTmWords, true);
+    tm_finish(a, &da, a->h_misc, 0, kCounterSlots / 2, CRDT_PLAN_SYNC);
+    tm_finish(b, &db, a->h_misc, kCounterSlots / 2, kCounterSlots / 2, CRDT_PLAN_SYNC);
     collect_timing(a);
-    *out_a = ra;
-    *out_b = rb;
-    return rb.status;
+    *out_a = da.res;
+    *out_b = db.res;
+    return db.res.status;
 }
 
-// ---- crdt_fanin_tables: for j < n_src: dst.merge(srcs[j].recordMap(since_j)) (table_merge.inc)
-// The composition itself: the crdt_merge_table calls of the contract, in call order, until one returns
-// non-zero; each step's row flags go into bit j of the mask.  Exact by construction; the fused form falls
-// back to it, with nothing written yet, whenever anything in the sequence may raise.
-static int fanin_tables_composed(crdt_ctx* dst, crdt_ctx* const* srcs, const int64_t* since, uint32_t n_src,
-                                 uint64_t n_rows, int64_t wall, uint8_t* win_mask, int32_t mask_mem,
-                                 crdt_result* out) {
+// ---- crdt_fanin_tables / crdt_fanout_tables: the composition itself, for both.  Step j of the sequence is
+// step[j].dst.merge(step[j].src.recordMap(since_j)): the crdt_merge_table calls of the contract, in call
+// order, until one returns non-zero; each step's row flags go into bit j of the mask, both staged in c's
+// scratch and on its stream.  Exact by construction; the fused forms fall back to it, with nothing written
+// yet, whenever anything in the sequence may raise.
+struct FanStep {
+    crdt_ctx *dst, *src;
+};
+
+static int fan_tables_composed(crdt_ctx* c, const FanStep* steps, const int64_t* since, uint32_t n,
+                               uint64_t n_rows, int64_t wall, uint8_t* win_mask, int32_t mask_mem,
+                               crdt_result* out) {
     uint8_t* step = nullptr;
     uint8_t* wm = win_mask;
     if (win_mask) {
-        HIPALLOC(dst->t_fstep.ensure(n_rows ? n_rows : 1));
-        step = dst->t_fstep.p;
+        HIPALLOC(c->t_fstep.ensure(n_rows ? n_rows : 1));
+        step = c->t_fstep.p;
         if (mask_mem == CRDT_MEM_HOST) {
-            HIPALLOC(dst->t_fmask.ensure(n_rows ? n_rows : 1));
-            wm = dst->t_fmask.p;
+            HIPALLOC(c->t_fmask.ensure(n_rows ? n_rows : 1));
+            wm = c->t_fmask.p;
         }
-        if (n_rows) HIPCHK(hipMemsetAsync(wm, 0, n_rows, dst->stream));
+        if (n_rows) HIPCHK(hipMemsetAsync(wm, 0, n_rows, c->stream));
     }
     int st = CRDT_OK;
-    for (uint32_t j = 0; j < n_src; ++j) {
-        st = crdt_merge_table(dst, srcs[j], n_rows, since[j], wall, step, CRDT_MEM_DEVICE, &out[j]);
+    for (uint32_t j = 0; j < n; ++j) {
+        st = crdt_merge_table(steps[j].dst, steps[j].src, n_rows, since[j], wall, step, CRDT_MEM_DEVICE, &out[j]);
         if (st >= 0 && win_mask && n_rows) {                  // (an error stores nothing: no bit)
-            k_fan_or_flags<<<std::min<uint32_t>(grid_for(n_rows, 256), 8192), 256, 0, dst->stream>>>(step, n_rows, j, wm);
+            k_fan_or_flags<<<std::min<uint32_t>(grid_for(n_rows, 256), 8192), 256, 0, c->stream>>>(step, n_rows, j, wm);
             HIPCHK(hipGetLastError());
+            if (j + 1 < n && steps[j + 1].dst != c)           // (the next step writes step[] on another stream)
+                HIPCHK(hipStreamSynchronize(c->stream));
         }
         if (st != 0) {                                        // an exception (or an error) ends the sequence
-            for (uint32_t k = j + 1; k < n_src; ++k) out[k] = cleared_result(dst->canonical);
+            for (uint32_t k = j + 1; k < n; ++k) out[k] = cleared_result(steps[k].dst->canonical);
             break;
         }
     }
     if (win_mask && n_rows) {
         if (mask_mem == CRDT_MEM_HOST)
-            HIPCHK(hipMemcpyAsync(win_mask, wm, n_rows, hipMemcpyDeviceToHost, dst->stream));
-        HIPCHK(hipStreamSynchronize(dst->stream));
+            HIPCHK(hipMemcpyAsync(win_mask, wm, n_rows, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
     }
     return st;
 }
 
+// ---- crdt_fanin_tables: for j < n_src: dst.merge(srcs[j].recordMap(since_j)) (table_merge.inc)
+// Its composition pairs dst with each source, staged on dst.
 int crdt_fanin_tables(crdt_ctx* dst, crdt_ctx* const* srcs, const int64_t* since_lt, uint32_t n_src,
                       uint64_t n_rows, int64_t wall, uint8_t* win_mask, int32_t mask_mem, crdt_result* out) {
-    if (!dst || !srcs || !since_lt || !out || n_src == 0 || n_src > CRDT_FANIN_MAX) return CRDT_E_INVALID;
-    for (uint32_t j = 0; j < n_src; ++j)
-        if (!srcs[j]) return CRDT_E_INVALID;                  // (every null check before a ctx is read)
-    bool self = false;
-    for (uint32_t j = 0; j < n_src; ++j) {
-        if (!tm_args_ok(dst, srcs[j], win_mask != nullptr, mask_mem) || n_rows > srcs[j]->cap) return CRDT_E_INVALID;
-        self |= srcs[j] == dst;
-    }
+    // the sources are a member list (a source twice is allowed); dst is on their device, and need not hold n_rows
+    if (!dst || !since_lt || !out || !tm_members_ok(srcs, n_src, CRDT_FANIN_MAX, n_rows, false) ||
+        !tm_args_ok(dst, srcs[0], win_mask != nullptr, mask_mem))
+        return CRDT_E_INVALID;
     if (n_src == 1) return crdt_merge_table(dst, srcs[0], n_rows, since_lt[0], wall, win_mask, mask_mem, out);
     HIPCHK(hipSetDevice(dst->device));
     if (dst->env_dynamic) read_env_knobs(dst);
+    FanStep steps[kFanMax];
+    bool self = false;
+    for (uint32_t j = 0; j < n_src; ++j) {
+        steps[j] = {dst, srcs[j]};
+        self |= srcs[j] == dst;
+    }
     // the composition: switched to, dst among its sources, or dst pinned to the sorted path (as crdt_merge_table)
     if (!dst->table_merge || self || dst->merge_path == CRDT_PATH_SORTED)
-        return fanin_tables_composed(dst, srcs, since_lt, n_src, n_rows, wall, win_mask, mask_mem, out);
+        return fan_tables_composed(dst, steps, since_lt, n_src, n_rows, wall, win_mask, mask_mem, out);
+    int st;
+    if ((st = tm_sync_others(dst, srcs, n_src))) return st;
     uint64_t rows[kFanMax], covered = 0;
     for (uint32_t j = 0; j < n_src; ++j) {
-        HIPCHK(hipStreamSynchronize(srcs[j]->stream));        // the sources' rows are final before dst's stream reads them
         rows[j] = ex_rows(srcs[j], n_rows, since_lt[j]);
         covered = std::max(covered, rows[j]);
     }
     const unsigned nb = grid_for(covered, kTmTile);
     uint8_t* rf;
-    int st;
     if ((st = tm_stage_flags(dst, win_mask, mask_mem, n_rows, &rf))) return st;
     if ((st = tm_begin(dst, nb, (int)n_src))) return st;
     // pass 1, once per source: its clock words, and its counts and bits over all nb tiles (zeros past its own
@@ -4738,27 +4759,22 @@ int crdt_fanin_tables(crdt_ctx* dst, crdt_ctx* const* srcs, const int64_t* since
     // selected id outside dst, or a send() that raises (the sequence ends there): nothing is written yet, the
     // composition gives the exact stop point, exception details and error
     FanArgs fa{};
-    crdt_result res[kFanMax];
+    TmDir d[kFanMax];
     int64_t c = c0;
     bool composed = false, has = false;
     for (uint32_t j = 0; j < n_src; ++j) {
-        const unsigned long long* wj = w + j * kTmWords;
-        composed |= wj[2] || (wj[3] && wj[1] > dst->cap);
-        has |= wj[3] != 0;
+        d[j] = tm_direction(c, w + j * kTmWords, dst->cap, wall);
+        composed |= d[j].needs_composition || d[j].res.status != CRDT_OK;
+        has |= d[j].has;
         fa.src[j] = srcs[j]->table;
         fa.rows[j] = rows[j];
-        fa.stamp[j] = tm_recv_canonical(c, wj);
-        res[j] = cleared_result(c);
-        res[j].n_stored = 1;
-        hlc_send(fa.stamp[j], wall).into(res[j]);
-        composed |= res[j].status != CRDT_OK;
-        c = res[j].canonical_lt;
+        fa.stamp[j] = d[j].stamp;
+        c = d[j].res.canonical_lt;
     }
-    if (composed) return fanin_tables_composed(dst, srcs, since_lt, n_src, n_rows, wall, win_mask, mask_mem, out);
+    if (composed) return fan_tables_composed(dst, steps, since_lt, n_src, n_rows, wall, win_mask, mask_mem, out);
     ev_record(dst, kEvClock);
     // pass 2: dst's row once, the sources folded over it in call order, the last winner stored
-    HIPALLOC(dst->t_fcounts.ensure(kFanCounts));
-    HIPCHK(hipMemsetAsync(dst->t_fcounts.p, 0, kFanCounts * sizeof(unsigned long long), dst->stream));
+    if ((st = tm_fan_counts_begin(dst))) return st;
     if ((st = tm_zero_uncovered(dst, rf, has ? covered : 0, n_rows))) return st;
     tm_apply_begin(dst, has);
     if (has) {
@@ -4768,71 +4784,23 @@ int crdt_fanin_tables(crdt_ctx* dst, crdt_ctx* const* srcs, const int64_t* since
     }
     tm_apply_end(dst, has);
     if ((st = tm_flags_to_host(dst, win_mask, rf, mask_mem, n_rows))) return st;
-    std::vector<unsigned long long> counts(kFanCounts);
-    HIPCHK(hipMemcpyAsync(counts.data(), dst->t_fcounts.p, kFanCounts * sizeof(unsigned long long),
-                          hipMemcpyDeviceToHost, dst->stream));
-    HIPCHK(hipStreamSynchronize(dst->stream));
     // per source: its counts from the call's own words (no Misc slots: tm_finish sums none), and on dst the
     // mark (it rises to the largest selected id of all), the canonical C_j and what crdt_last_plan reports
+    if ((st = tm_fan_counts_end(dst, d, n_src))) return st;
     for (uint32_t j = 0; j < n_src; ++j) {
-        const unsigned long long* cj = counts.data() + 2 * j * kCounterSlots;
-        for (int s = 0; s < kCounterSlots; ++s) {
-            res[j].n_present += cj[s];
-            res[j].n_won += cj[kCounterSlots + s];
-        }
-        tm_finish(dst, &res[j], dst->h_misc, 0, 0, w + j * kTmWords, false);
-        out[j] = res[j];
+        tm_finish(dst, &d[j], dst->h_misc, 0, 0, 0);
+        out[j] = d[j].res;
     }
-    dst->last_fanin = true;
+    dst->last_table_plan |= CRDT_PLAN_FANIN;
     collect_timing(dst);
     return CRDT_OK;
 }
 
 // ---- crdt_fanout_tables: for j < n_dst: dsts[j].merge(src.recordMap(since_j)) (table_merge.inc)
-// The composition itself: the crdt_merge_table calls of the contract, in call order, until one returns
-// non-zero; each step's row flags go into bit j of the mask (staged on dsts[0], as fanin_tables_composed
-// stages on dst).  Exact by construction; the fused form falls back to it, with nothing written yet.
-static int fanout_tables_composed(crdt_ctx* src, crdt_ctx* const* dsts, const int64_t* since, uint32_t n_dst,
-                                  uint64_t n_rows, int64_t wall, uint8_t* win_mask, int32_t mask_mem,
-                                  crdt_result* out) {
-    crdt_ctx* d0 = dsts[0];
-    uint8_t* step = nullptr;
-    uint8_t* wm = win_mask;
-    if (win_mask) {
-        HIPALLOC(d0->t_fstep.ensure(n_rows ? n_rows : 1));
-        step = d0->t_fstep.p;
-        if (mask_mem == CRDT_MEM_HOST) {
-            HIPALLOC(d0->t_fmask.ensure(n_rows ? n_rows : 1));
-            wm = d0->t_fmask.p;
-        }
-        if (n_rows) HIPCHK(hipMemsetAsync(wm, 0, n_rows, d0->stream));
-    }
-    int st = CRDT_OK;
-    for (uint32_t j = 0; j < n_dst; ++j) {
-        st = crdt_merge_table(dsts[j], src, n_rows, since[j], wall, step, CRDT_MEM_DEVICE, &out[j]);
-        if (st >= 0 && win_mask && n_rows) {                  // (an error stores nothing: no bit)
-            k_fan_or_flags<<<std::min<uint32_t>(grid_for(n_rows, 256), 8192), 256, 0, d0->stream>>>(step, n_rows, j, wm);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipStreamSynchronize(d0->stream));         // (the next step writes step[] on another stream)
-        }
-        if (st != 0) {                                        // an exception (or an error) ends the sequence
-            for (uint32_t k = j + 1; k < n_dst; ++k) out[k] = cleared_result(dsts[k]->canonical);
-            break;
-        }
-    }
-    if (win_mask && n_rows) {
-        if (mask_mem == CRDT_MEM_HOST)
-            HIPCHK(hipMemcpyAsync(win_mask, wm, n_rows, hipMemcpyDeviceToHost, d0->stream));
-        HIPCHK(hipStreamSynchronize(d0->stream));
-    }
-    return st;
-}
-
+// Its composition pairs each destination with src, staged on dsts[0].
 int crdt_fanout_tables(crdt_ctx* src, crdt_ctx* const* dsts, const int64_t* since_lt, uint32_t n_dst,
                        uint64_t n_rows, int64_t wall, uint8_t* win_mask, int32_t mask_mem, crdt_result* out) {
-    if (!src || !dsts || !since_lt || !out || n_dst == 0 || n_dst > CRDT_FANOUT_MAX) return CRDT_E_INVALID;
-    for (uint32_t j = 0; j < n_dst; ++j)
-        if (!dsts[j]) return CRDT_E_INVALID;                  // (every null check before a ctx is read)
+    if (!src || !since_lt || !out || !tm_list_ok(dsts, n_dst, CRDT_FANOUT_MAX)) return CRDT_E_INVALID;
     for (uint32_t j = 0; j < n_dst; ++j)
         if (!tm_args_ok(dsts[j], src, win_mask != nullptr, mask_mem)) return CRDT_E_INVALID;
     if (n_rows > src->cap) return CRDT_E_INVALID;
@@ -4841,17 +4809,20 @@ int crdt_fanout_tables(crdt_ctx* src, crdt_ctx* const* dsts, const int64_t* sinc
     HIPCHK(hipSetDevice(d0->device));
     // the composition: a destination switched to it or pinned to the sorted path (as crdt_merge_table), src
     // among the destinations, or one of them twice (its merges are then not independent)
+    FanStep steps[kFoMax];
     bool composed = false;
     for (uint32_t j = 0; j < n_dst; ++j) {
         crdt_ctx* d = dsts[j];
+        steps[j] = {d, src};
         if (d->env_dynamic) read_env_knobs(d);
         composed |= !d->table_merge || d == src || d->merge_path == CRDT_PATH_SORTED;
         for (uint32_t k = 0; k < j; ++k) composed |= dsts[k] == d;
     }
-    if (composed) return fanout_tables_composed(src, dsts, since_lt, n_dst, n_rows, wall, win_mask, mask_mem, out);
+    if (composed) return fan_tables_composed(d0, steps, since_lt, n_dst, n_rows, wall, win_mask, mask_mem, out);
     // src's rows are final before d0's stream reads them, and nothing is queued on a table it writes
+    int st;
     HIPCHK(hipStreamSynchronize(src->stream));
-    for (uint32_t j = 1; j < n_dst; ++j) HIPCHK(hipStreamSynchronize(dsts[j]->stream));
+    if ((st = tm_sync_others(d0, dsts, n_dst))) return st;
     FoArgs fa{};
     uint64_t covered = 0;
     for (uint32_t j = 0; j < n_dst; ++j) {
@@ -4865,7 +4836,6 @@ int crdt_fanout_tables(crdt_ctx* src, crdt_ctx* const* dsts, const int64_t* sinc
     }
     const unsigned nb = grid_for(covered, kTmTile);
     uint8_t* rf;
-    int st;
     if ((st = tm_stage_flags(d0, win_mask, mask_mem, n_rows, &rf))) return st;
     if ((st = tm_begin(d0, nb, (int)n_dst))) return st;
     // pass 1: src's {lt, rank, mod} once; every destination's counts, bits and clock words from it
@@ -4879,23 +4849,18 @@ int crdt_fanout_tables(crdt_ctx* src, crdt_ctx* const* dsts, const int64_t* sinc
     // per destination: R_j = max(C_j, max lt of its selection), C_j' = Hlc.send(R_j).  A row that may raise in
     // its recv(), a selected id outside it, or a send() that raises (the sequence ends there): nothing is
     // written yet, the composition gives the exact stop point, exception details and error
-    crdt_result res[kFoMax];
+    TmDir d[kFoMax];
     bool has = false;
     for (uint32_t j = 0; j < n_dst; ++j) {
-        const unsigned long long* wj = w + j * kTmWords;
-        composed |= wj[2] || (wj[3] && wj[1] > dsts[j]->cap);
-        has |= wj[3] != 0;
-        fa.stamp[j] = tm_recv_canonical(fa.canonical[j], wj);
-        res[j] = cleared_result(fa.canonical[j]);
-        res[j].n_stored = 1;
-        hlc_send(fa.stamp[j], wall).into(res[j]);
-        composed |= res[j].status != CRDT_OK;
+        d[j] = tm_direction(fa.canonical[j], w + j * kTmWords, dsts[j]->cap, wall);
+        composed |= d[j].needs_composition || d[j].res.status != CRDT_OK;
+        has |= d[j].has;
+        fa.stamp[j] = d[j].stamp;
     }
-    if (composed) return fanout_tables_composed(src, dsts, since_lt, n_dst, n_rows, wall, win_mask, mask_mem, out);
+    if (composed) return fan_tables_composed(d0, steps, since_lt, n_dst, n_rows, wall, win_mask, mask_mem, out);
     ev_record(d0, kEvClock);
     // pass 2: src's selected rows once, every destination's winners stored from them
-    HIPALLOC(d0->t_fcounts.ensure(kFanCounts));
-    HIPCHK(hipMemsetAsync(d0->t_fcounts.p, 0, kFanCounts * sizeof(unsigned long long), d0->stream));
+    if ((st = tm_fan_counts_begin(d0))) return st;
     if ((st = tm_zero_uncovered(d0, rf, has ? covered : 0, n_rows))) return st;
     tm_apply_begin(d0, has);
     if (has) {
@@ -4905,21 +4870,13 @@ int crdt_fanout_tables(crdt_ctx* src, crdt_ctx* const* dsts, const int64_t* sinc
     }
     tm_apply_end(d0, has);
     if ((st = tm_flags_to_host(d0, win_mask, rf, mask_mem, n_rows))) return st;
-    std::vector<unsigned long long> counts(kFanCounts);
-    HIPCHK(hipMemcpyAsync(counts.data(), d0->t_fcounts.p, kFanCounts * sizeof(unsigned long long),
-                          hipMemcpyDeviceToHost, d0->stream));
-    HIPCHK(hipStreamSynchronize(d0->stream));
     // per destination: its counts from the call's own words (no Misc slots: tm_finish sums none), its mark,
     // its canonical C_j' and what crdt_last_plan reports
+    if ((st = tm_fan_counts_end(d0, d, n_dst))) return st;
     for (uint32_t j = 0; j < n_dst; ++j) {
-        const unsigned long long* cj = counts.data() + 2 * j * kCounterSlots;
-        for (int s = 0; s < kCounterSlots; ++s) {
-            res[j].n_present += cj[s];
-            res[j].n_won += cj[kCounterSlots + s];
-        }
-        tm_finish(dsts[j], &res[j], d0->h_misc, 0, 0, w + j * kTmWords, false);
-        dsts[j]->last_fanout = true;
-        out[j] = res[j];
+        tm_finish(dsts[j], &d[j], d0->h_misc, 0, 0, 0);
+        dsts[j]->last_table_plan |= CRDT_PLAN_FANOUT;
+        out[j] = d[j].res;
     }
     collect_timing(d0);
     return CRDT_OK;
@@ -4982,27 +4939,67 @@ int crdt_digest_rows(crdt_ctx* c, uint64_t n_rows, uint64_t block_rows, int32_t 
     return CRDT_OK;
 }
 
+// ---- crdt_tombstone_live: Crdt.clear() (crdt.dart:67-73) on the table (table_live.inc).  What
+// crdt_export_since at 0, a filter on val and crdt_put_stamped of the live ids leave, in one pass: Hlc.send is
+// taken first, the pass stores its stamp over the live rows, and the canonical moves only if there was one
+// (no live row: nothing was written, the no-op of crdt.dart:48).  A send that raises stores nothing: whether
+// it is reported depends on a live row alone, so the count pass answers it.
+int crdt_tombstone_live(crdt_ctx* c, uint64_t n_rows, int64_t wall, uint8_t* row_flags, int32_t flags_mem,
+                        crdt_result* out) {
+    if (!c || !out || n_rows > c->cap || c->has_comm ||
+        (row_flags && flags_mem != CRDT_MEM_HOST && flags_mem != CRDT_MEM_DEVICE))
+        return CRDT_E_INVALID;
+    crdt_result res = cleared_result(c->canonical);
+    HIPCHK(hipSetDevice(c->device));
+    uint8_t* rf;
+    int st;
+    if ((st = tm_stage_flags(c, row_flags, flags_mem, n_rows, &rf))) return st;
+    const uint64_t rows = ex_rows(c, n_rows, 0);      // (the rows from the high-water mark on are fill: not live)
+    const HlcSend send = hlc_send(c->canonical, wall);
+    unsigned long long live = 0;
+    if (send.status != CRDT_OK) {
+        uint64_t n_sel = 0, n_live = 0;
+        if ((st = crdt_count_since(c, n_rows, 0, &n_sel, &n_live))) return st;
+        live = n_live;
+        if (rf && n_rows) HIPCHK(hipMemsetAsync(rf, 0, n_rows, c->stream));
+    } else {
+        unsigned long long* word = reinterpret_cast<unsigned long long*>(c->d_word.p);
+        if (rows) {
+            HIPCHK(hipMemsetAsync(word, 0, sizeof(*word), c->stream));
+            const unsigned nb = grid_for(rows, kTmTile);
+            k_lv_tombstone<<<std::min(nb, kLvGrid), kTmThreads, 0, c->stream>>>(c->table, rows, nb, send.canonical,
+                                                                                c->local_rank, rf, word);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpyAsync(&live, word, sizeof(live), hipMemcpyDeviceToHost, c->stream));
+        }
+        if ((st = tm_zero_uncovered(c, rf, rows, n_rows))) return st;
+    }
+    if ((st = tm_flags_to_host(c, row_flags, rf, flags_mem, n_rows))) return st;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (live && send.status != CRDT_OK) {
+        send.into(res);
+    } else if (live) {
+        c->canonical = send.canonical;
+        res.canonical_lt = send.canonical;
+        res.n_won = live;
+    }
+    *out = res;
+    return res.status;
+}
+
 // ---- crdt_purge_tombstones: the tombstones every member holds alike, dropped from all of them (table_purge.inc)
 int crdt_purge_tombstones(crdt_ctx* const* ctxs, uint32_t n_ctx, uint64_t n_rows, int64_t before_lt,
                           uint8_t* row_flags, int32_t flags_mem, crdt_purge* out) {
-    if (!ctxs || !out || n_ctx == 0 || n_ctx > CRDT_PURGE_MAX) return CRDT_E_INVALID;
-    for (uint32_t j = 0; j < n_ctx; ++j)
-        if (!ctxs[j]) return CRDT_E_INVALID;              // (every null check before a ctx is read)
+    if (!out || !tm_members_ok(ctxs, n_ctx, CRDT_PURGE_MAX, n_rows, true) ||
+        (row_flags && flags_mem != CRDT_MEM_HOST && flags_mem != CRDT_MEM_DEVICE))
+        return CRDT_E_INVALID;
     crdt_ctx* c0 = ctxs[0];
-    if (row_flags && flags_mem != CRDT_MEM_HOST && flags_mem != CRDT_MEM_DEVICE) return CRDT_E_INVALID;
-    for (uint32_t j = 0; j < n_ctx; ++j) {
-        const crdt_ctx* c = ctxs[j];
-        if (c->device != c0->device || c->has_comm || n_rows > c->cap) return CRDT_E_INVALID;
-        for (uint32_t k = 0; k < j; ++k)
-            if (ctxs[k] == c) return CRDT_E_INVALID;      // (a row would have two owners)
-    }
     crdt_purge r = {0, 0};
     if (n_rows == 0) { *out = r; return CRDT_OK; }
     HIPCHK(hipSetDevice(c0->device));
-    // every member's rows are final before c0's stream reads and writes them
-    for (uint32_t j = 1; j < n_ctx; ++j) HIPCHK(hipStreamSynchronize(ctxs[j]->stream));
     uint8_t* rf;
     int st;
+    if ((st = tm_sync_others(c0, ctxs, n_ctx))) return st;
     if ((st = tm_stage_flags(c0, row_flags, flags_mem, n_rows, &rf))) return st;
     const uint64_t rows = ex_rows(c0, n_rows, 0);         // (member 0's rows from its high-water mark on are fill)
     unsigned long long w[2] = {0, 0};
@@ -5016,7 +5013,7 @@ int crdt_purge_tombstones(crdt_ctx* const* ctxs, uint32_t n_ctx, uint64_t n_rows
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(w, words, sizeof(w), hipMemcpyDeviceToHost, c0->stream));
     }
-    if (rf && n_rows > rows) HIPCHK(hipMemsetAsync(rf + rows, 0, n_rows - rows, c0->stream));
+    if ((st = tm_zero_uncovered(c0, rf, rows, n_rows))) return st;
     if ((st = tm_flags_to_host(c0, row_flags, rf, flags_mem, n_rows))) return st;
     HIPCHK(hipStreamSynchronize(c0->stream));
     r.n_candidates = w[0];
@@ -5028,26 +5025,18 @@ int crdt_purge_tombstones(crdt_ctx* const* ctxs, uint32_t n_ctx, uint64_t n_rows
 // ---- crdt_diff_group: the read-only comparison of up to 8 replicas in one pass (table_group.inc)
 int crdt_diff_group(crdt_ctx* const* ctxs, uint32_t n_ctx, uint64_t n_rows, uint8_t* behind_mask, uint8_t* hold_mask,
                     uint8_t* conflict_flags, int32_t flags_mem, crdt_group_diff* out) {
-    if (!ctxs || !out || n_ctx == 0 || n_ctx > CRDT_GROUP_MAX) return CRDT_E_INVALID;
-    for (uint32_t j = 0; j < n_ctx; ++j)
-        if (!ctxs[j]) return CRDT_E_INVALID;              // (every null check before a ctx is read)
-    crdt_ctx* c0 = ctxs[0];
     uint8_t* const host[3] = {behind_mask, hold_mask, conflict_flags};
-    if ((host[0] || host[1] || host[2]) && flags_mem != CRDT_MEM_HOST && flags_mem != CRDT_MEM_DEVICE)
+    if (!out || !tm_members_ok(ctxs, n_ctx, CRDT_GROUP_MAX, n_rows, true) ||
+        ((host[0] || host[1] || host[2]) && flags_mem != CRDT_MEM_HOST && flags_mem != CRDT_MEM_DEVICE))
         return CRDT_E_INVALID;
-    for (uint32_t j = 0; j < n_ctx; ++j) {
-        const crdt_ctx* c = ctxs[j];
-        if (c->device != c0->device || c->has_comm || n_rows > c->cap) return CRDT_E_INVALID;
-        for (uint32_t k = 0; k < j; ++k)
-            if (ctxs[k] == c) return CRDT_E_INVALID;
-    }
+    crdt_ctx* c0 = ctxs[0];
     crdt_group_diff r;
     memset(&r, 0, sizeof(r));
     r.first_diff = UINT64_MAX;
     if (n_rows == 0) { *out = r; return CRDT_OK; }
     HIPCHK(hipSetDevice(c0->device));
-    // every member's rows are final before c0's stream reads them
-    for (uint32_t j = 1; j < n_ctx; ++j) HIPCHK(hipStreamSynchronize(ctxs[j]->stream));
+    int st;
+    if ((st = tm_sync_others(c0, ctxs, n_ctx))) return st;
     uint8_t* dev[3] = {behind_mask, hold_mask, conflict_flags};
     if (flags_mem == CRDT_MEM_HOST && (host[0] || host[1] || host[2])) {   // one [n_rows] part per array passed
         size_t parts = 0;
@@ -5066,10 +5055,8 @@ int crdt_diff_group(crdt_ctx* const* ctxs, uint32_t n_ctx, uint64_t n_rows, uint
     const unsigned nb = grid_for(n_rows, kTmTile);
     k_gd_diff<<<std::min(nb, kDfGrid), kTmThreads, 0, c0->stream>>>(ga, n_ctx, n_rows, nb, dev[0], dev[1], dev[2], words);
     HIPCHK(hipGetLastError());
-    for (int k = 0; k < 3; ++k) {
-        int st;
+    for (int k = 0; k < 3; ++k)
         if ((st = tm_flags_to_host(c0, host[k], dev[k], flags_mem, n_rows))) return st;
-    }
     unsigned long long w[kGdWords];
     HIPCHK(hipMemcpyAsync(w, words, sizeof(w), hipMemcpyDeviceToHost, c0->stream));
     HIPCHK(hipStreamSynchronize(c0->stream));
@@ -5105,9 +5092,8 @@ int crdt_last_path(const crdt_ctx* c, int* path) {
 int crdt_last_plan(const crdt_ctx* c, uint32_t* flags) {
     if (!c || !flags) return CRDT_E_INVALID;
     uint32_t f = 0;
-    if (c->last_table) {
-        *flags = CRDT_PLAN_TABLE | (c->last_sync ? CRDT_PLAN_SYNC : 0u) | (c->last_fanin ? CRDT_PLAN_FANIN : 0u) |
-                 (c->last_fanout ? CRDT_PLAN_FANOUT : 0u);
+    if (c->last_table_plan) {
+        *flags = c->last_table_plan;
         return CRDT_OK;
     }
     if (c->last_sorted) {

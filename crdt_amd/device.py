@@ -271,8 +271,7 @@ class DeviceTable:
         """``self.merge(src.recordMap(modifiedSince))`` between two tables of one device and one id
         space: src's export is merged as ONE device changeset, nothing crossing to the host.
         Returns (result dict, win flags) as ``merge`` does for a device batch."""
-        if src.device != self.device:
-            raise ValueError(f"merge_from: the source table is on device {src.device}, this one on {self.device}")
+        self._on_device((src,), "merge_from", "the source")
         ex = src.export_since(n_rows, since)
         offs = np.array([0, ex.n], np.uint64)
         v = ex._view
@@ -281,14 +280,29 @@ class DeviceTable:
         import torch
         return self._merge_batch(b, ex.n, torch.device("cuda", self.device), wall, win_flags)
 
+    def _on_device(self, tables, method: str, noun: str):
+        """Every table of ``tables`` is on this one's device, or ValueError ("<method>: <noun> table is on ...")."""
+        for t in tables:
+            if t.device != self.device:
+                raise ValueError(f"{method}: {noun} table is on device {t.device}, this one on {self.device}")
+
+    def _ctx_array(self, tables, method: str, noun: str, lead=()):
+        """The C array of the ctx pointers of ``lead`` then ``tables`` (never of zero length), the ``tables``
+        checked by ``_on_device``."""
+        self._on_device(tables, method, noun)
+        ptrs = [t._ctx.value for t in (*lead, *tables)]
+        return (ctypes.c_void_p * max(len(ptrs), 1))(*ptrs)
+
     def _row_flags_arg(self, row_flags, n_rows: int):
-        """(array to return, pointer, memory kind) of a ``row_flags`` argument of merge_table / sync_tables."""
+        """(array to return, pointer, memory kind) of a ``row_flags`` argument of the table calls.  For True the
+        array is the ``n_rows`` entries of a new device tensor (never an empty allocation)."""
         flags_arr, fptr, mem = None, None, _capi.CRDT_MEM_DEVICE
         if row_flags is True:
             import torch
-            flags_arr = torch.zeros(max(n_rows, 1), dtype=torch.uint8, device=torch.device("cuda", self.device))
-            torch_ready(flags_arr)                      # (its zero fill must not land after the merge)
-            fptr = ctypes.c_void_p(flags_arr.data_ptr())
+            full = torch.zeros(max(n_rows, 1), dtype=torch.uint8, device=torch.device("cuda", self.device))
+            torch_ready(full)                           # (its zero fill must not land after the merge)
+            fptr = ctypes.c_void_p(full.data_ptr())
+            flags_arr = full[:n_rows]
         elif row_flags is not None and row_flags is not False:
             flags_arr = row_flags
             if _is_torch(row_flags):
@@ -309,16 +323,13 @@ class DeviceTable:
         this table's row was stored.  ``row_flags``: True -> a torch uint8 tensor on the table's device;
         a torch uint8 CUDA tensor -> filled in place; a numpy uint8 array -> host memory, filled in place;
         False/None -> not produced."""
-        if src.device != self.device:
-            raise ValueError(f"merge_table: the source table is on device {src.device}, this one on {self.device}")
+        self._on_device((src,), "merge_table", "the source")
         n_rows = int(n_rows)
         flags_arr, fptr, mem = self._row_flags_arg(row_flags, n_rows)
         res = CrdtResult()
         st = self._lib.crdt_merge_table(self._ctx, src._ctx, n_rows, int(since), int(wall), fptr, mem,
                                         ctypes.byref(res))
         self._check(st, "crdt_merge_table")
-        if row_flags is True:
-            flags_arr = flags_arr[:n_rows]
         return res.as_dict(), flags_arr
 
     def sync_tables(self, other: "DeviceTable", n_rows: int, since_self: int, since_other: int, wall: int,
@@ -328,8 +339,7 @@ class DeviceTable:
         tables (``crdt_sync_tables``); exactly what the two ``merge_table`` calls leave, the second skipped
         when the first raises.  Returns ((result of self, its row flags), (result of other, its row flags)).
         ``row_flags``: as ``merge_table``'s, or a pair (for self, for other) of arrays of one memory kind."""
-        if other.device != self.device:
-            raise ValueError(f"sync_tables: the other table is on device {other.device}, this one on {self.device}")
+        self._on_device((other,), "sync_tables", "the other")
         n_rows = int(n_rows)
         rf_self, rf_other = row_flags if isinstance(row_flags, (tuple, list)) else (row_flags, row_flags)
         arr_a, ptr_a, mem_a = self._row_flags_arg(rf_self, n_rows)
@@ -341,10 +351,6 @@ class DeviceTable:
         st = self._lib.crdt_sync_tables(self._ctx, other._ctx, n_rows, int(since_self), int(since_other), int(wall),
                                         ptr_a, ptr_b, mem, ctypes.byref(res_a), ctypes.byref(res_b))
         self._check(st, "crdt_sync_tables")
-        if rf_self is True:
-            arr_a = arr_a[:n_rows]
-        if rf_other is True:
-            arr_b = arr_b[:n_rows]
         return (res_a.as_dict(), arr_a), (res_b.as_dict(), arr_b)
 
     def merge_tables(self, srcs, n_rows: int, sinces, wall: int, win_mask=False):
@@ -353,22 +359,22 @@ class DeviceTable:
         what the ``merge_table`` calls leave, the sequence ending at the first that raises.  Returns (list of
         result dicts, one per source; mask or None): ``mask[i]`` has bit j set where merge j stored row i.
         ``win_mask``: as ``merge_table``'s ``row_flags``."""
-        srcs, sinces = list(srcs), [int(s) for s in sinces]
-        if len(sinces) != len(srcs):
-            raise ValueError(f"merge_tables: {len(srcs)} sources but {len(sinces)} sinces")
-        for s in srcs:
-            if s.device != self.device:
-                raise ValueError(f"merge_tables: a source table is on device {s.device}, this one on {self.device}")
-        n_rows, n_src = int(n_rows), len(srcs)
+        return self._fan_tables("merge_tables", "crdt_fanin_tables", "source", srcs, n_rows, sinces, wall, win_mask)
+
+    def _fan_tables(self, method: str, entry: str, noun: str, tables, n_rows: int, sinces, wall: int, win_mask):
+        """``merge_tables`` / ``fanout_tables``: this table against ``tables`` (the ``noun`` tables) through the
+        C entry point ``entry``."""
+        tables, sinces = list(tables), [int(s) for s in sinces]
+        if len(sinces) != len(tables):
+            raise ValueError(f"{method}: {len(tables)} {noun}s but {len(sinces)} sinces")
+        n_rows, n = int(n_rows), len(tables)
+        ctxs = self._ctx_array(tables, method, f"a {noun}")
         mask_arr, mptr, mem = self._row_flags_arg(win_mask, n_rows)
-        ctxs = (ctypes.c_void_p * max(n_src, 1))(*(s._ctx.value for s in srcs))
-        since_arr = (ctypes.c_int64 * max(n_src, 1))(*sinces)
-        res = (CrdtResult * max(n_src, 1))()
-        st = self._lib.crdt_fanin_tables(self._ctx, ctxs, since_arr, n_src, n_rows, int(wall), mptr, mem, res)
-        self._check(st, "crdt_fanin_tables")
-        if win_mask is True:
-            mask_arr = mask_arr[:n_rows]
-        return [res[j].as_dict() for j in range(n_src)], mask_arr
+        since_arr = (ctypes.c_int64 * max(n, 1))(*sinces)
+        res = (CrdtResult * max(n, 1))()
+        st = getattr(self._lib, entry)(self._ctx, ctxs, since_arr, n, n_rows, int(wall), mptr, mem, res)
+        self._check(st, entry)
+        return [res[j].as_dict() for j in range(n)], mask_arr
 
     def fanout_tables(self, dsts, n_rows: int, sinces, wall: int, win_mask=False):
         """The hub's outbound half, called on the SOURCE: ``for d, since in zip(dsts, sinces):
@@ -377,22 +383,8 @@ class DeviceTable:
         the sequence ending at the first that raises.  Returns (list of result dicts, one per destination; mask
         or None): ``mask[i]`` has bit j set where destination j stored row i.  ``win_mask``: as
         ``merge_table``'s ``row_flags``."""
-        dsts, sinces = list(dsts), [int(s) for s in sinces]
-        if len(sinces) != len(dsts):
-            raise ValueError(f"fanout_tables: {len(dsts)} destinations but {len(sinces)} sinces")
-        for d in dsts:
-            if d.device != self.device:
-                raise ValueError(f"fanout_tables: a destination table is on device {d.device}, this one on {self.device}")
-        n_rows, n_dst = int(n_rows), len(dsts)
-        mask_arr, mptr, mem = self._row_flags_arg(win_mask, n_rows)
-        ctxs = (ctypes.c_void_p * max(n_dst, 1))(*(d._ctx.value for d in dsts))
-        since_arr = (ctypes.c_int64 * max(n_dst, 1))(*sinces)
-        res = (CrdtResult * max(n_dst, 1))()
-        st = self._lib.crdt_fanout_tables(self._ctx, ctxs, since_arr, n_dst, n_rows, int(wall), mptr, mem, res)
-        self._check(st, "crdt_fanout_tables")
-        if win_mask is True:
-            mask_arr = mask_arr[:n_rows]
-        return [res[j].as_dict() for j in range(n_dst)], mask_arr
+        return self._fan_tables("fanout_tables", "crdt_fanout_tables", "destination", dsts, n_rows, sinces, wall,
+                                win_mask)
 
     def diff_table(self, other: "DeviceTable", n_rows: int, flags=False):
         """The read-only comparison of this replica (a) with ``other`` (b) over rows [0, n_rows)
@@ -401,15 +393,12 @@ class DeviceTable:
         hold one byte per ROW id, ``_capi.DIFF_A_AHEAD`` where this table holds the winning record,
         ``DIFF_B_AHEAD`` where ``other`` does, ``DIFF_CONFLICT`` where both hold one (lt, rank) with different
         values, and feed ``export_flagged``.  ``flags``: as ``merge_table``'s ``row_flags``."""
-        if other.device != self.device:
-            raise ValueError(f"diff_table: the other table is on device {other.device}, this one on {self.device}")
+        self._on_device((other,), "diff_table", "the other")
         n_rows = int(n_rows)
         flags_arr, fptr, mem = self._row_flags_arg(flags, n_rows)
         d = _capi.CrdtDiff()
         self._check(self._lib.crdt_diff_tables(self._ctx, other._ctx, n_rows, fptr, mem, ctypes.byref(d)),
                     "crdt_diff_tables")
-        if flags is True:
-            flags_arr = flags_arr[:n_rows]
         return d.as_dict(), flags_arr
 
     def digest_rows(self, n_rows: int, block_rows: int = 1 << 20, state: bool = False) -> np.ndarray:
@@ -462,8 +451,6 @@ class DeviceTable:
         res = CrdtResult()
         st = self._lib.crdt_tombstone_live(self._ctx, n_rows, int(wall), fptr, mem, ctypes.byref(res))
         self._check(st, "crdt_tombstone_live")
-        if row_flags is True:
-            flags_arr = flags_arr[:n_rows]
         return res.as_dict(), flags_arr
 
     def purge_tombstones(self, others, n_rows: int, before: int, row_flags=False):
@@ -476,18 +463,12 @@ class DeviceTable:
         is touched.  Returns ({"n_candidates", "n_purged"}, row flags or None): the flags are indexed by ROW
         id, one byte for each of ``n_rows`` rows, 1 where the row was purged (they feed ``export_flagged`` on
         any member).  ``row_flags``: as ``merge_table``'s."""
-        others = list(others)
-        for t in others:
-            if t.device != self.device:
-                raise ValueError(f"purge_tombstones: a member table is on device {t.device}, this one on {self.device}")
-        n_rows, n_ctx = int(n_rows), 1 + len(others)
+        ctxs = self._ctx_array(list(others), "purge_tombstones", "a member", lead=(self,))
+        n_rows = int(n_rows)
         flags_arr, fptr, mem = self._row_flags_arg(row_flags, n_rows)
-        ctxs = (ctypes.c_void_p * n_ctx)(self._ctx.value, *(t._ctx.value for t in others))
         out = _capi.CrdtPurge()
-        st = self._lib.crdt_purge_tombstones(ctxs, n_ctx, n_rows, int(before), fptr, mem, ctypes.byref(out))
+        st = self._lib.crdt_purge_tombstones(ctxs, len(ctxs), n_rows, int(before), fptr, mem, ctypes.byref(out))
         self._check(st, "crdt_purge_tombstones")
-        if row_flags is True:
-            flags_arr = flags_arr[:n_rows]
         return out.as_dict(), flags_arr
 
     def diff_group(self, others, n_rows: int, masks=False):
@@ -502,11 +483,8 @@ class DeviceTable:
         ``export_flagged``.  ``masks``: False/None -> no array (three ``None``); True -> three torch uint8 tensors
         on the table's device; a triple (behind, hold, conflict) whose entries are each as ``merge_table``'s
         ``row_flags``, the arrays that are passed all in one memory (host or device)."""
-        others = list(others)
-        for t in others:
-            if t.device != self.device:
-                raise ValueError(f"diff_group: a member table is on device {t.device}, this one on {self.device}")
-        n_rows, n_ctx = int(n_rows), 1 + len(others)
+        ctxs = self._ctx_array(list(others), "diff_group", "a member", lead=(self,))
+        n_rows = int(n_rows)
         want = tuple(masks) if isinstance(masks, (tuple, list)) else (masks,) * 3
         if len(want) != 3:
             raise ValueError("diff_group: masks is True, False or a triple (behind, hold, conflict)")
@@ -515,12 +493,11 @@ class DeviceTable:
         if len(mems) > 1:
             raise ValueError("diff_group: the mask arrays must live in the same memory (host or device)")
         mem = mems.pop() if mems else _capi.CRDT_MEM_DEVICE
-        ctxs = (ctypes.c_void_p * n_ctx)(self._ctx.value, *(t._ctx.value for t in others))
         out = _capi.CrdtGroupDiff()
-        st = self._lib.crdt_diff_group(ctxs, n_ctx, n_rows, args[0][1], args[1][1], args[2][1], mem, ctypes.byref(out))
+        st = self._lib.crdt_diff_group(ctxs, len(ctxs), n_rows, args[0][1], args[1][1], args[2][1], mem,
+                                       ctypes.byref(out))
         self._check(st, "crdt_diff_group")
-        arrs = [(arr[:n_rows] if m is True else arr) for m, (arr, _, _) in zip(want, args)]
-        return out.as_dict(), arrs[0], arrs[1], arrs[2]
+        return out.as_dict(), args[0][0], args[1][0], args[2][0]
 
     def _batch(self, key, lt, rank, val, offsets, millis):
         c = _Cols(self.device, key=(key, "u4"), lt=(lt, "i8"), rank=(rank, "u4"), val=(val, "u4"), millis=(millis, "i8"))
