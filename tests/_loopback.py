@@ -3,7 +3,8 @@ all-gather repeats rank 0's row, the reductions keep its words, and the all-to-a
 peer d, a device copy (hipMemcpyAsync on the ctx stream) of exactly the bytes rank 0 sends d.  It drives
 the library's device-memory collective path (the one RCCL takes: no host synchronisation inside the
 collectives) on one GPU; tools/route_probe.py times it, tests/test_gpu_parity.py checks that every way of
-routing leaves the same rows under it.  Test / tool infrastructure."""
+routing leaves the same rows under it.  The device-memory transport that has real peers, every rank with
+its own data and checked against the oracle, is tests/_thread_comm.py.  Test / tool infrastructure."""
 import ctypes
 
 from crdt_amd import _capi

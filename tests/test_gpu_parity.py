@@ -251,12 +251,15 @@ def _init_pg(dist, rank, world, backend):
 
 def _make_injected(kw):
     """make_case(**kw) with an optional record that raises at (41, 123,456): kw["inject"] = "drift"
-    (millis past wall + 60 s) or "dup" (the local node id, above every clock the call reaches)."""
+    (millis past wall + 60 s) or "dup" (the local node id, above every clock the call reaches);
+    kw["inject_at"] = (changeset, index): another place, for cases smaller than that."""
     kw = dict(kw)
     inject = kw.pop("inject", None)
+    at_j, at_i = kw.pop("inject_at", (41, 123_456))
     case = make_case(**kw)
     if inject:
-        x = int(case["offsets"][41]) + 123_456
+        assert at_i < int(case["offsets"][at_j + 1] - case["offsets"][at_j])
+        x = int(case["offsets"][at_j]) + at_i
         case["lt"] = case["lt"].copy()
         case["rank"] = case["rank"].copy()
         if inject == "drift":
@@ -327,6 +330,28 @@ def _shard_gpu_worker(rank, world, port, case_kw, kind, q, backend="gloo", path=
         dist.destroy_process_group()
 
 
+def check_shards(case, outs, world, kind, path, counts, orows, ores, oflags):
+    """Every rank's result fields, every row of every shard and (gather / sorted+flags) the reassembled win
+    flags against the oracle's unsharded merge of ``case``; outs: (rank, res, lt, rk, val, mod, sel, fl) per
+    rank, whatever communicator moved the records."""
+    flags = np.zeros(len(case["key"]), np.uint8)
+    for rank, res, lt, rk, val, mod, sel, fl in outs:
+        for f in RESULT_FIELDS:
+            if f in ("n_present", "n_won") and not counts and res["path"] == "sorted":
+                assert res[f] == (1 << 64) - 1
+                continue
+            assert res[f] == ores[f], (kind, rank, f, res[f], ores[f])
+        if fl is not None:
+            flags[sel] = fl
+        keys = np.arange(case["n_ids"])
+        mine = keys % world == rank
+        slots = keys[mine] // world
+        for f, a in (("lt", lt), ("rank", rk), ("val", val), ("mod", mod)):
+            assert np.array_equal(a[slots], orows[f][mine]), (kind, f)
+    if path in ("gather", "sorted+flags"):
+        assert np.array_equal(flags, oflags)
+
+
 def run_shard_gpu(kw, world, kind, backend="gloo", path="gather", counts=True, again=False):
     import torch.multiprocessing as mp
 
@@ -344,22 +369,7 @@ def run_shard_gpu(kw, world, kind, backend="gloo", path="gather", counts=True, a
     for p in procs:
         p.join(timeout=60)
         assert p.exitcode == 0
-    flags = np.zeros(len(case["key"]), np.uint8)
-    for rank, res, lt, rk, val, mod, sel, fl in outs:
-        for f in RESULT_FIELDS:
-            if f in ("n_present", "n_won") and not counts and res["path"] == "sorted":
-                assert res[f] == (1 << 64) - 1
-                continue
-            assert res[f] == ores[f], (kind, rank, f, res[f], ores[f])
-        if fl is not None:
-            flags[sel] = fl
-        keys = np.arange(case["n_ids"])
-        mine = keys % world == rank
-        slots = keys[mine] // world
-        for f, a in (("lt", lt), ("rank", rk), ("val", val), ("mod", mod)):
-            assert np.array_equal(a[slots], orows[f][mine]), (kind, f)
-    if path in ("gather", "sorted+flags"):
-        assert np.array_equal(flags, oflags)
+    check_shards(case, outs, world, kind, path, counts, orows, ores, oflags)
     return outs
 
 
