@@ -517,14 +517,11 @@ int l2_prep(crdt_ctx* c, Rl1Scratch& os, uint32_t ngrp, uint32_t nsrc, const uin
     HIPALLOC(os.rec2.ensure((3 * pos + 3) / 4 + kPartPad));             // 12-B payloads
     HIPALLOC(os.kj2.ensure(pos / 4 + 1 + kPartPad));                      // 1-B key column
     // the packed resolve's work items and split buckets' part states
-    const uint32_t nb = ngrp * kDigits;
-    const uint32_t max_items = nb + (uint32_t)(pos / kRPart) + 1;
-    const size_t ksn = (size_t)(2 * (pos / kRPart) + 2) * kSKeys;
-    const uint32_t max_hot = std::min<uint32_t>(nb, (uint32_t)(pos / kRPart) + 1);
-    HIPALLOC(os.ibase.ensure(2 * (nb + 1) + 1 + max_hot));
-    HIPALLOC(os.kslt.ensure(ksn));
-    HIPALLOC(os.ksu32.ensure(ksn));
-    HIPALLOC(os.ibucket.ensure(max_items));
+    const ItemGeom g = item_geom(ngrp * kDigits, pos);
+    HIPALLOC(os.ibase.ensure(g.ibase_units));
+    HIPALLOC(os.kslt.ensure(g.ksn));
+    HIPALLOC(os.ksu32.ensure(g.ksn));
+    HIPALLOC(os.ibucket.ensure(g.max_items));
     return CRDT_OK;
 }
 
@@ -541,27 +538,18 @@ int l2_launch(crdt_ctx* c, Rl1Scratch& os, hipStream_t stream) {
     const uint64_t* d_spos = os.plan.p + 2 * nsg + os.u32w;
     const TileMap tm2{d_gbeg, d_gend, d_tb2, os.tseg.p, nullptr, (uint32_t)nsg, (uint32_t)kPTile2};
     const ScanMap sm2{d_stb, d_scb, d_spos, ngrp};
-    const bool rev = c->xcd_map && !(c->form_off & kFormNoReverse);
     if (nt2) {
         k_seg_index<<<std::min<uint32_t>(grid_for(nt2, 256), 4096), 256, 0, stream>>>(d_tb2, (uint32_t)nsg, nt2,
                                                                                      os.tseg.p);
-        if (c->rl1_cmp)          // the compact form: 1-B level-2 digits beside the 12-B records
-            k_part_hist16w<256, kPTile2, true><<<nt2, 256, 0, stream>>>(c->rl_k16.p, tm2, 0, os.hist.p);
-        else
-            k_part_hist16w<256, kPTile2><<<nt2, 256, 0, stream>>>(c->rl_k16.p, tm2, kSBits - 4, os.hist.p);
+        // (the compact form: 1-B level-2 digits beside the 12-B records)
+        launch_l2_hist(c->rl1_cmp ? kH2Digit8 : kH2Wide8K, c->rl_k16.p, tm2, nt2, c, os.hist.p, stream);
         k_scan_part<<<nc2, 256, 0, stream>>>(os.hist.p, sm2, os.part.p);
     }
     k_scan_seg<<<ngrp, 256, 0, stream>>>(os.part.p, sm2, os.choff.p, os.dstart2.p, nullptr);
     if (nt2) {
         k_scan_tiles<<<nc2, 256, 0, stream>>>(os.hist.p, os.choff.p, sm2, os.dstart2.p, os.toff.p);
-        const uint32_t xper2 = c->xcd_map ? (nt2 + kXcds - 1) / kXcds : 0;
-        if (c->rl1_cmp)
-            k_part_scatter2<false, true, true, true, true, true><<<xcd_grid(nt2, c->xcd_map), kPThreads, 0, stream>>>(
-                c->rl_rec.p, nullptr, tm2, 24, os.toff.p, os.rec2.p, nullptr, xper2, rev ? os.hist.p : nullptr);
-        else
-            k_part_scatter2<false, true, true, true><<<xcd_grid(nt2, c->xcd_map), kPThreads, 0, stream>>>(
-                c->rl_rec.p, c->rl_k16.p, tm2, kSBits - 4, os.toff.p, os.rec2.p, os.kj2.p, xper2,
-                rev ? os.hist.p : nullptr);
+        launch_scatter2(false, true, c->rl1_cmp, true, true, c->rl_rec.p, c->rl_k16.p, tm2, nt2, os.toff.p, os.rec2.p,
+                               os.kj2.p, c->xcd_map, form_reverse(c) ? os.hist.p : nullptr, stream);
     }
     HIPCHK(hipGetLastError());
     return CRDT_OK;
@@ -593,38 +581,17 @@ int rl1_owner_launch(crdt_ctx* c, Rl1Scratch& os, const PackFrame& pf, hipStream
     int st = l2_launch(c, os, stream);
     if (st) return st;
     if (timed) ev_record(c, ev_window(2, true));
-    const uint32_t nb = os.ngrp * kDigits;
-    const uint32_t* bst = os.dstart2.p;
-    const uint32_t max_items = nb + (uint32_t)(nw / kRPart) + 1;
-    const uint32_t max_hot = std::min<uint32_t>(nb, (uint32_t)(nw / kRPart) + 1);
-    uint32_t* d_ib = os.ibase.p;
-    uint32_t* d_hb = os.ibase.p + nb + 1;
-    uint32_t* d_hot = os.ibase.p + 2 * (nb + 1);
-    uint64_t* ps_key = reinterpret_cast<uint64_t*>(os.kslt.p);
-    uint32_t* ps_val = os.ksu32.p;
-    const Rec12* rec12 = reinterpret_cast<const Rec12*>(os.rec2.p);
-    const void* rv = os.kj2.p;
+    const ItemGeom g = item_geom(os.ngrp * kDigits, nw, os.ibase.p);
+    const PackedItems a{os.dstart2.p, g, os.ibucket.p, reinterpret_cast<const Rec12*>(os.rec2.p), os.kj2.p, c->table,
+                        c->cap, c->d_Rj.p, reinterpret_cast<uint64_t*>(os.kslt.p), os.ksu32.p, pf, c->d_misc};
     if (timed) ev_record(c, ev_window(3, false));
-    k_bucket_items<<<(nb + 1023) / 1024, 1024, 0, stream>>>(bst, nb, d_ib, d_hb, d_hot, c->d_misc);
-    k_seg_index<<<std::min<uint32_t>(grid_for(max_items, 256), 4096), 256, 0, stream>>>(d_ib, nb, max_items, os.ibucket.p);
-    if (c->rl1_cmp)
-        k_resolve_packed<true, true, false, false, true><<<max_items, kQThreads, 0, stream>>>(
-            bst, d_ib, d_hb, os.ibucket.p, nb, rec12, nullptr, c->table, c->cap, hw, c->d_Rj.p, 0, ps_key, ps_val, pf,
-            c->d_misc);
-    else
-        k_resolve_packed<true, true, true><<<max_items, kQThreads, 0, stream>>>(
-            bst, d_ib, d_hb, os.ibucket.p, nb, rec12, rv, c->table, c->cap, hw, c->d_Rj.p, 0, ps_key, ps_val, pf,
-            c->d_misc);
-    k_part_carry_packed<false><<<dim3(kSKeys / 256, max_hot), 256, 0, stream>>>(
-        d_hot, d_ib, d_hb, c->table, c->cap, hw, ps_key, ps_val, c->d_Rj.p, 0, pf, c->d_misc);
-    if (c->rl1_cmp)
-        k_resolve_packed<false, true, false, false, true><<<max_items, kQThreads, 0, stream>>>(
-            bst, d_ib, d_hb, os.ibucket.p, nb, rec12, nullptr, c->table, c->cap, hw, c->d_Rj.p, 0, ps_key, ps_val, pf,
-            c->d_misc, EmitOut{}, c->sparse_t);
-    else
-        k_resolve_packed<false, true, true><<<max_items, kQThreads, 0, stream>>>(
-            bst, d_ib, d_hb, os.ibucket.p, nb, rec12, rv, c->table, c->cap, hw, c->d_Rj.p, 0, ps_key, ps_val, pf,
-            c->d_misc, EmitOut{}, c->sparse_t);
+    k_bucket_items<<<(g.nb + 1023) / 1024, 1024, 0, stream>>>(a.bst, g.nb, g.ib, g.hb, g.hot, c->d_misc);
+    k_seg_index<<<std::min<uint32_t>(grid_for(g.max_items, 256), 4096), 256, 0, stream>>>(g.ib, g.nb, g.max_items,
+                                                                                        os.ibucket.p);
+    launch_packed_fold(a, c->rl1_cmp, true, g.max_items, stream, hw, 0, nullptr);
+    k_part_carry_packed<false><<<dim3(kSKeys / 256, g.max_hot), 256, 0, stream>>>(
+        g.hot, g.ib, g.hb, c->table, c->cap, hw, a.ps_key, a.ps_val, c->d_Rj.p, 0, pf, c->d_misc);
+    launch_packed_dense(a, c->rl1_cmp, true, true, g.max_items, stream, hw, 0, nullptr, c->sparse_t, false);
     if (timed) ev_record(c, ev_window(3, true));
     HIPCHK(hipGetLastError());
     return CRDT_OK;
@@ -729,9 +696,8 @@ int rl1_head_prep(crdt_ctx* c, uint32_t P, uint32_t Dh, const std::vector<uint64
     if (st) return st;
     const uint64_t nw = c->rl_hf.nw;
     const uint32_t nb = GD * kDigits;
-    const uint32_t max_items = nb + (uint32_t)(nw / kRPart) + 1;
-    const uint32_t max_hot = std::min<uint32_t>(nb, (uint32_t)(nw / kRPart) + 1);
-    const uint32_t n_items = max_items + max_hot * (kSKeys / 256);
+    const ItemGeom g = item_geom(nb, nw);
+    const uint32_t n_items = g.max_items + g.max_hot * (kSKeys / 256);
     const size_t slots = (size_t)std::min<uint64_t>(nw, (uint64_t)nb * kSKeys) + 1;
     HIPALLOC(c->e_bbase.ensure(nb));
     HIPALLOC(c->e_key.ensure(slots));
@@ -758,11 +724,8 @@ int rl1_head_launch(crdt_ctx* c, const PackFrame& pf, uint32_t Dh, uint64_t own_
     const uint32_t G = c->n_ranks, me = c->rank, GD = G * Dh;
     int st = l2_launch(c, hf, stream);
     if (st) return st;
-    const uint64_t nw = hf.nw;
-    const uint32_t nb = GD * kDigits;
-    const uint32_t max_items = nb + (uint32_t)(nw / kRPart) + 1;
-    const uint32_t max_hot = std::min<uint32_t>(nb, (uint32_t)(nw / kRPart) + 1);
-    const uint32_t n_items = max_items + max_hot * (kSKeys / 256);
+    const ItemGeom g = item_geom(GD * kDigits, hf.nw, hf.ibase.p);
+    const uint32_t n_items = g.max_items + g.max_hot * (kSKeys / 256);
     EmitOut eo{};
     eo.G = GD;                                          // one emit "owner" per group (o, d)
     eo.osh = 20;
@@ -773,36 +736,19 @@ int rl1_head_launch(crdt_ctx* c, const PackFrame& pf, uint32_t Dh, uint64_t own_
     eo.icount = c->e_icnt.p;
     eo.ibase = c->e_icnt.p + n_items;
     eo.ocount = c->e_icnt.p + 2 * (size_t)n_items;
-    eo.item0 = max_items;
+    eo.item0 = g.max_items;
     eo.n_items = n_items;
     HIPCHK(hipMemsetAsync(c->e_icnt.p, 0, (size_t)n_items * (2 + GD) * sizeof(uint32_t), stream));
-    const uint32_t* bst = hf.dstart2.p;
-    uint32_t* d_ib = hf.ibase.p;
-    uint32_t* d_hb = hf.ibase.p + nb + 1;
-    uint32_t* d_hot = hf.ibase.p + 2 * (nb + 1);
-    uint64_t* ps_key = reinterpret_cast<uint64_t*>(hf.kslt.p);
-    uint32_t* ps_val = hf.ksu32.p;
-    const Rec12* rec12 = reinterpret_cast<const Rec12*>(hf.rec2.p);
     const uint64_t hcap = (uint64_t)GD << 20;           // rows g << 20 | low slot bits, all absent (hw = 0: no table)
-    k_bucket_items<<<(nb + 1023) / 1024, 1024, 0, stream>>>(bst, nb, d_ib, d_hb, d_hot, c->d_misc, c->e_bbase.p);
-    k_seg_index<<<std::min<uint32_t>(grid_for(max_items, 256), 4096), 256, 0, stream>>>(d_ib, nb, max_items, hf.ibucket.p);
-    if (c->rl1_cmp) {
-        k_resolve_packed<true, true, false, false, true><<<max_items, kQThreads, 0, stream>>>(
-            bst, d_ib, d_hb, hf.ibucket.p, nb, rec12, nullptr, c->table, hcap, 0, c->d_Rj.p, 0, ps_key, ps_val, pf,
-            c->d_misc);
-        k_resolve_packed<false, false, false, true, true><<<max_items, kQThreads, 0, stream>>>(
-            bst, d_ib, d_hb, hf.ibucket.p, nb, rec12, nullptr, c->table, hcap, 0, c->d_Rj.p, 0, ps_key, ps_val, pf,
-            c->d_misc, eo);
-    } else {
-        k_resolve_packed<true, true, true><<<max_items, kQThreads, 0, stream>>>(
-            bst, d_ib, d_hb, hf.ibucket.p, nb, rec12, hf.kj2.p, c->table, hcap, 0, c->d_Rj.p, 0, ps_key, ps_val, pf,
-            c->d_misc);
-        k_resolve_packed<false, false, true, true><<<max_items, kQThreads, 0, stream>>>(
-            bst, d_ib, d_hb, hf.ibucket.p, nb, rec12, hf.kj2.p, c->table, hcap, 0, c->d_Rj.p, 0, ps_key, ps_val, pf,
-            c->d_misc, eo);
-    }
-    k_part_carry_packed<true><<<dim3(kSKeys / 256, max_hot), 256, 0, stream>>>(
-        d_hot, d_ib, d_hb, c->table, hcap, 0, ps_key, ps_val, c->d_Rj.p, 0, pf, c->d_misc, eo);
+    const PackedItems a{hf.dstart2.p, g, hf.ibucket.p, reinterpret_cast<const Rec12*>(hf.rec2.p), hf.kj2.p, c->table,
+                        hcap, c->d_Rj.p, reinterpret_cast<uint64_t*>(hf.kslt.p), hf.ksu32.p, pf, c->d_misc};
+    k_bucket_items<<<(g.nb + 1023) / 1024, 1024, 0, stream>>>(a.bst, g.nb, g.ib, g.hb, g.hot, c->d_misc, c->e_bbase.p);
+    k_seg_index<<<std::min<uint32_t>(grid_for(g.max_items, 256), 4096), 256, 0, stream>>>(g.ib, g.nb, g.max_items,
+                                                                                        hf.ibucket.p);
+    launch_packed_fold(a, c->rl1_cmp, true, g.max_items, stream, 0, 0, nullptr);
+    launch_packed_emit(a, c->rl1_cmp, true, g.max_items, stream, 0, eo);
+    k_part_carry_packed<true><<<dim3(kSKeys / 256, g.max_hot), 256, 0, stream>>>(
+        g.hot, g.ib, g.hb, c->table, hcap, 0, a.ps_key, a.ps_val, c->d_Rj.p, 0, pf, c->d_misc, eo);
     unsigned long long* d_tot = c->e_cnt.p + 2;
     const uint32_t nch = (n_items + kCombChunk - 1) / kCombChunk;
     k_comb_chunk_sum<<<nch, 256, 0, stream>>>(eo.ocount, n_items, GD, c->e_csum.p);
@@ -1004,7 +950,7 @@ int route_l1(crdt_ctx* c, const Cols& cols, const uint64_t* offsets, int64_t wal
     HIPCHK(hipEventRecord(c->route_ev, c->stream));
     // every piece partitioned on the side stream, in order, behind the scans (the ctx stream stays free for
     // the collectives)
-    const bool rev = c->xcd_map && !(c->form_off & kFormNoReverse);
+    const bool rev = form_reverse(c);
     HIPCHK(hipEventRecord(c->rl_evo, c->stream));
     HIPCHK(hipStreamWaitEvent(c->sstream, c->rl_evo, 0));
     for (uint32_t q = 0; q < P; ++q) {

@@ -2835,664 +2835,714 @@ void place_drop(crdt_ctx* c) {
     c->place_best = 0;
 }
 
-// Sorted path (sorted_path.inc) for the whole batch: k_resolve (stop point), then per
-// window of kWindow changesets a level-1 (+ level-2) partition of the applied records and
-// the per-bucket LDS resolve.  sg = the batch's changeset segments (host), in changeset
-// order; one changeset may be several segments (records routed in from several ranks).
+// ---- the sorted apply: its form, the launch helpers it shares with comm_path.inc, its phases ----
+// The compiler puts template kernels into the code object in the order the host code first names them.  This list
+// names the sorted path's in the order they have had so far, so the device code does not depend on how the host
+// code below (and in comm_path.inc) is arranged: a host-only change still leaves the device assembly identical.
+#define K(...) (const void*)(__VA_ARGS__)
+#define S1(...) K(k_part_scatter1<__VA_ARGS__>)
+const void* const kSortedKernelOrder[] = {
+    K(k_part_hist<true>), S1(true, false, true, kL1Items, true, true, true, true, true),
+    S1(true, false, true, kL1Items, true, true, true, true), S1(kL1Items),
+    S1(true, false, true, kL1Items, true, true, false, true), S1(true, false, true, kL1Items, true, true, true),
+    S1(true, false, false, kL1Items, true, false, true), S1(true, true, true, kL1Items, true),
+    S1(true, true, false, kL1Items, true), S1(true, false, true, kL1Items, true), S1(true, false, true),
+    S1(true, false, false, kL1Items, true), S1(false, false, false, kL1Items, true),
+    K(k_part_hist16w<256, kPTile2, true>), K(k_part_hist16w<256, kPTile2>), K(k_part_hist16w<>),
+    K(k_part_hist<false, true>), K(k_part_hist<false>), K(k_part_scatter2_seg<true, true, true>),
+    K(k_part_scatter2_seg<true, true>), K(k_part_scatter2_seg<true, false>), K(k_part_scatter2_seg<false, false>),
+    K(k_part_scatter2<true, false>), K(k_part_scatter2<false, true, true, true, true, true>),
+    K(k_part_scatter2<false, true, true, true>), K(k_part_scatter2<false, true, true>), K(k_part_scatter2<false, true>),
+    K(k_part_scatter2<false, false>), K(k_resolve_packed<true, true, true>),
+    K(k_resolve_packed<false, false, true, true>), K(k_resolve_packed<true>),
+    K(k_resolve_packed<false, false, false, true>), K(k_part_carry_packed<true>),
+    K(k_resolve_packed<true, true, false, false, true>), K(k_resolve_pflags<false, true>), K(k_resolve_pflags<true>),
+    K(k_resolve_pflags<false>), K(k_flags_back_pre<false, 6, kPTile2, 16>),
+    K(k_flags_back_pre<false, 6, kPTile2, 32, 256>), K(k_flags_back<false, 6, kPTile2, true>),
+    K(k_flags_back<false, 6, kPTile, true>), K(k_flags_back<false, 4, kPTile2, false>),
+    K(k_flags_back<false, 4, kPTile, false>), K(k_flags_back<false, 6, kPTile2, false>),
+    K(k_flags_back<false, 6, kPTile, false>), K(k_flags_back<false, 0, kPTile2, false>),
+    K(k_flags_back<false, 0, kPTile, false>), K(k_flags_back_pre<true, 6, kPTile, 14, 512, true>),
+    K(k_flags_back_pre<true, 6, kPTile, 14>), K(k_flags_back<true, 6, kPTile, true>),
+    K(k_flags_back<true, 4, kPTile, false>), K(k_flags_back<true, 6, kPTile, false>),
+    K(k_flags_back<true, 0, kPTile, false>), K(k_resolve<true>), K(k_part_carry<false>), K(k_resolve<false>),
+    K(k_part_carry_packed<false>), K(k_resolve_packed<false, true, false, false, true>),
+    K(k_resolve_packed<false, false, true>), K(k_resolve_packed<false, false>), K(k_resolve_packed<false, true, true>),
+    K(k_resolve_packed<false>), K(k_resolve_sparse<false, true>), K(k_resolve_sparse<true, false>),
+    K(k_resolve_sparse<false, false>), K(k_resolve<true, true>), K(k_part_carry<true>), K(k_resolve<false, true>),
+    K(k_resolve_packed<false, false, false, true, true>),
+};
+#undef K
+#undef S1
+
+// The flag passes: k_flags_back_pre, or k_flags_back with four-byte staging (wide) or byte staging with a checkpoint
+// per 16 / 64 staged bytes / none (CRDT_FBACK_CHK).  The level-2 histogram: the compact form's 1-B digits; the 2-B
+// key column with wave-private bins (8K- / 32K-record tiles) or shared bins; the 4-B kj words.
+enum FlagPass : uint8_t { kFpPre, kFpWide, kFpChk4, kFpChk6, kFpChk0 };
+enum L2Hist : uint8_t { kH2Digit8, kH2Wide8K, kH2Wide, kH2Key16, kH2Kj };
+
+inline bool form_reverse(const crdt_ctx* c) { return c->xcd_map && !(c->form_off & kFormNoReverse); }
+
+// The form of one sorted apply, decided once per call (sorted_form) from the ctx's switches, the batch's frame and
+// CRDT_SORTED_FORM; the phases read the form, never the switches.
+struct SortedForm {
+    bool fl = false, em = false;    // flagged (flags carried back to input order) / emit (map-side combine)
+    bool two = false;               // two partition levels (capacity > 2^20)
+    bool pk = false, ord = false;   // packed 12-B payloads + packed resolve; its ordered form (flags, exact counts)
+    bool k8 = false, k16 = false;   // 1-B final key column (the packed key leaves 4 bits free); 2-B level-1 one
+    bool cmp = false;               // the compact form (PackFrame::cb): 12-B records carrying their level-1 slot
+    bool pt1 = false;               // flagged, compact, one window: level-1 positions tile-strided (kPT)
+    bool ov = false;                // split buckets' folds on the side stream, beside the unsplit buckets' resolve
+    bool rev = false, vec1 = false; // reverse fill of every other tile range; level-1 scatter with vector loads
+    bool whole_lines = false, lists = false, spk = false;   // packed resolve: whole lines, item lists, sparse kernel
+    bool fback_xcd = false, fp2_512 = false;   // flag passes in XCD tile order; the level-2 pre pass in 512 threads
+    bool hw = false;                // the packed resolve skips the rows >= hw_read (in the first window)
+    FlagPass fp1 = kFpPre, fp2 = kFpPre;   // the level-1 (unless pt1) and level-2 flag pass
+    L2Hist h2 = kH2Kj;
+    uint32_t ts2 = 0, shift1 = 0;   // records per level-2 tile; the level-1 digit's first key bit
+    uint32_t win = kWindow;         // changesets per window: kWindow (the kj word's field), the packed key's W
+    PackFrame pf{};
+};
+
+// One window of the call: what the loop gives it, then what sorted_win_plan and sorted_level2 leave for later phases.
+struct SortedWin {
+    size_t s0 = 0;                  // segments [s0, s0 + nseg), changesets [jb, jb + win), nw records
+    uint32_t nseg = 0, jb = 0;
+    uint64_t nw = 0;
+    bool first = false, only = false, ph = false;   // the call's first / only window; phase events
+    uint32_t nt1 = 0, nc1 = 0, nt2 = 0, nc2 = 0;    // (plan) tiles and scan chunks per level (level 2: upper bounds)
+    size_t rec_units = 0, kj2_units = 0;
+    TileMap tm1{};
+    ScanMap sm1z{};                 // level 1's scan from position 0
+    bool h1 = false, hotp = false;  // the level-1 histogram is the scan's; its hot bins are digits of their own (HotL1)
+    uint32_t hb = 0;                // hot bins the scan counted apart, and their records
+    uint64_t hot_n = 0;
+    const uint32_t* hist1 = nullptr;
+    TileMap tm2{};                  // (sorted_level2) level 2's tiling, for the flag pass
+};
+
+int sorted_form(crdt_ctx* c, const Cols& cols, const Segs& sg, bool fl, bool em, SortedForm* out) {
+    SortedForm f;
+    const uint32_t fo = c->form_off;
+    f.fl = fl; f.em = em;
+    f.two = c->cap > (1ull << 20);
+    f.shift1 = f.two ? 20u : (uint32_t)kSBits;
+    // order-free form: packed 12-B payloads and the packed resolve when the scan's frame of the
+    // batch fits the 64-bit key (one read-back of Misc per call), else wide payloads + lists
+    if (cols.packed_in || (c->packed_resolve && c->frame_on)) {
+        HIPCHK(hipMemcpyAsync(c->h_misc, c->d_misc, sizeof(Misc), hipMemcpyDeviceToHost, c->stream));
+        SYNCHK(c, c->stream);
+        f.pf = frame_of(c);
+        f.pk = f.pf.ok;
+        if (cols.packed_in && !f.pk) return CRDT_E_INVALID;         // routed packed under this same frame
+    }
+    if ((fl || em) && (!f.pk || cols.packed_in)) return CRDT_E_INVALID;   // the callers checked the frame
+    // (without flags: no positions kept, no flags carried back)
+    f.ord = !em && (fl || (c->counts && f.pk && !cols.packed_in));
+    f.k8 = f.pk && f.two && f.pf.key4 && !(fo & kFormNoKey8);
+    f.k16 = f.k8 && !(fo & kFormNoKey16);
+    // the compact form (round 6; sorted_path.inc PackFrame::cb): on one ctx's order-free packed form, when the
+    // records' lt & 0xFFFF (the scan's fr_cmax) leave the lt field short enough, 12-B records that carry their
+    // whole 20-bit level-1 slot (+ a 1-B level-2 digit column at level 1) instead of 14 + 13 B
+    if (f.k16 && (f.ord || !c->counts) && !em && !c->has_comm && !cols.packed_in && c->frame_on &&
+        !(fo & (kFormNoCompact | kFormNoHistW | kFormBigTile2 | kFormNoWholeLines | kFormNoVecLoads))) {
+        const PackFrame cf = compact_frame(f.pf, (uint32_t)std::min<unsigned long long>(c->h_misc->fr_cmax, 0xFFFFull),
+                                           c->plan_R);
+        if (cf.cb) { f.pf = cf; f.cmp = true; }
+    }
+    f.hw = f.pk && (!c->counts || f.ord) && c->hw_read < c->cap;
+    f.win = f.pk ? f.pf.jwin : kWindow;
+    f.fback_xcd = c->xcd_map && (fo & kFormFbackXcd);
+    const size_t ns = sg.j.size();
+    f.pt1 = fl && f.cmp && ns && sg.j[0] / f.win == sg.j[ns - 1] / f.win &&
+            !(fo & (kFormNoPosT | kFormNoFbackPre | kFormFbackWide)) && !f.fback_xcd;
+    f.rev = form_reverse(c);
+    f.vec1 = !(fo & kFormNoVecLoads);
+    // level-2 tiles of the packed form: kPTile2 records (one sub-tile each) — 256 workgroups
+    // then cover a short stretch of each level-1 bucket at a time
+    const bool hw16 = f.k16 && !(fo & kFormNoHistW);
+    f.ts2 = hw16 && !(fo & kFormBigTile2) ? (uint32_t)kPTile2 : (uint32_t)kPTile;
+    f.h2 = f.cmp ? kH2Digit8 : hw16 ? (f.ts2 == (uint32_t)kPTile2 ? kH2Wide8K : kH2Wide) : f.k16 ? kH2Key16 : kH2Kj;
+    f.whole_lines = !(fo & kFormNoWholeLines);
+    f.lists = !c->has_comm && !(fo & kFormNoItemLists) && (f.ord || f.whole_lines);
+    f.spk = c->sparse_t > 0 && !(fo & kFormNoSparseK) && f.whole_lines;
+    f.ov = !em && f.pk && (f.ord || !c->counts) && f.two && (fo & kFormOverlap);
+    const FlagPass chk = c->fback_chk == 4 ? kFpChk4 : c->fback_chk == 6 ? kFpChk6 : kFpChk0;
+    f.fp1 = !(fo & (kFormNoFbackPre | kFormFbackWide)) && !f.fback_xcd ? kFpPre : (fo & kFormFbackWide) ? kFpWide : chk;
+    f.fp2 = f.fp1 == kFpPre && f.ts2 != (uint32_t)kPTile2 ? chk : f.fp1;   // (k_flags_back_pre: 8K-record tiles)
+    f.fp2_512 = (fo & kFormFbackPre512) != 0;
+    // what crdt_last_plan reports (sorted_window adds each window's level-1 histogram choices)
+    c->last_ordered = f.ord; c->last_packed = f.pk; c->last_compact = f.cmp;
+    c->last_key8 = f.k8; c->last_key16 = f.k16; c->last_hw = f.hw;
+    c->last_hist1_fused = c->last_hot_direct = false;
+    c->key_end_valid = true;                 // k_bucket_items bounds the rows every window writes
+    *out = f;
+    return CRDT_OK;
+}
+
+// The resolve's work items over nb final buckets of nw records: parts of buckets (one of more than kRPart records
+// is split), ksn part-state slots of split buckets, and k_bucket_items' arrays in one buffer of ibase_units words:
+// the item prefix, the part-state prefix, the split buckets ([0]: their count).
+struct ItemGeom {
+    uint32_t nb, max_items, max_hot;
+    size_t ksn, ibase_units;
+    uint32_t *ib, *hb, *hot;
+    void bind(uint32_t* ibase) { ib = ibase; hb = ibase + nb + 1; hot = ibase + 2 * (nb + 1); }
+};
+inline ItemGeom item_geom(uint32_t nb, uint64_t nw, uint32_t* ibase = nullptr) {
+    const uint32_t max_hot = std::min<uint32_t>(nb, (uint32_t)(nw / kRPart) + 1);   // split buckets hold > kRPart
+    ItemGeom g{nb, nb + (uint32_t)(nw / kRPart) + 1, max_hot, (size_t)(2 * (nw / kRPart) + 2) * kSKeys,
+               2 * ((size_t)nb + 1) + 1 + max_hot, nullptr, nullptr, nullptr};
+    if (ibase) g.bind(ibase);
+    return g;
+}
+
+// One resolve's items and what its kernels share; k_resolve_packed has one launcher per pass.  cmp / k8: the record
+// form (compact: no key column; 1-B key column; 4-B kj words).  Kernels called through a pointer get every argument.
+struct PackedItems {
+    const uint32_t* bst;                // [nb + 1] the buckets' first records
+    ItemGeom g;
+    const uint32_t* ibucket;            // [items] bucket of each item (k_seg_index)
+    const Rec12* rec;                   // the final records (the list forms': u32x4) and their key column
+    const void* kj;
+    Table table;                        // (cap: the rows' key range)
+    uint64_t cap;
+    const int64_t* Rj;
+    uint64_t* ps_key;                   // part states
+    uint32_t* ps_val;
+    PackFrame pf;
+    const Misc* misc;
+};
+using PackedFn = decltype(&k_resolve_packed<true>);
+inline void launch_packed(PackedFn k, const PackedItems& a, bool cmp, uint32_t grid, hipStream_t s, uint64_t hw,
+                          uint32_t jb, const EmitOut& eo, uint32_t sparse_t, bool sparse_skip, const uint32_t* list) {
+    k<<<grid, kQThreads, 0, s>>>(a.bst, a.g.ib, a.g.hb, a.ibucket, a.g.nb, a.rec, cmp ? nullptr : a.kj, a.table, a.cap,
+                                 hw, a.Rj, jb, a.ps_key, a.ps_val, a.pf, a.misc, eo, sparse_t, sparse_skip, list);
+}
+// split buckets: each part folded alone -> part states
+void launch_packed_fold(const PackedItems& a, bool cmp, bool k8, uint32_t grid, hipStream_t s, uint64_t hw,
+                        uint32_t jb, const uint32_t* list) {
+    const PackedFn k = cmp ? k_resolve_packed<true, true, false, false, true>
+                     : k8 ? k_resolve_packed<true, true, true> : k_resolve_packed<true>;
+    launch_packed(k, a, cmp, grid, s, hw, jb, EmitOut{}, 0, false, list);
+}
+// unsplit buckets against the table's rows; !whole_lines (never compact): changed rows only, over every item slot
+void launch_packed_dense(const PackedItems& a, bool cmp, bool k8, bool whole_lines, uint32_t grid, hipStream_t s,
+                         uint64_t hw, uint32_t jb, const uint32_t* list, uint32_t sparse_t, bool sparse_skip) {
+    if (!whole_lines) {
+        const PackedFn k = k8 ? k_resolve_packed<false, false, true> : k_resolve_packed<false, false>;
+        launch_packed(k, a, false, a.g.max_items, s, hw, jb, EmitOut{}, 0, false, nullptr);
+        return;
+    }
+    const PackedFn k = cmp ? k_resolve_packed<false, true, false, false, true>
+                     : k8 ? k_resolve_packed<false, true, true> : k_resolve_packed<false>;
+    launch_packed(k, a, cmp, grid, s, hw, jb, EmitOut{}, sparse_t, sparse_skip, list);
+}
+// unsplit buckets against an absent table (hw = 0): every key's maximum emitted
+void launch_packed_emit(const PackedItems& a, bool cmp, bool k8, uint32_t grid, hipStream_t s, uint32_t jb,
+                        const EmitOut& eo) {
+    const PackedFn k = cmp ? k_resolve_packed<false, false, false, true, true>
+                     : k8 ? k_resolve_packed<false, false, true, true> : k_resolve_packed<false, false, false, true>;
+    launch_packed(k, a, cmp, grid, s, 0, jb, eo, 0, false, nullptr);
+}
+
+// Level-1 scatter: the form's kernel on the window's tiling, between its phase and placement-trial events.
+int sorted_l1_scatter(crdt_ctx* c, const SortedForm& f, const Cols& cols, const SortedWin& w) {
+    if (w.ph) ev_record(c, ev_window(1, false));
+    if (c->place_timed && w.first) HIPCHK(hipEventRecord(c->place_ev[0], c->stream));   // (the first window)
+    if (f.pt1) HIPALLOC(c->f_pos1.ensure((size_t)w.nt1 * kPTile + 16));   // tile t's positions at t * kPTile
+    const uint32_t grid = xcd_grid(w.nt1, c->xcd_map);
+    const uint32_t xper1 = c->xcd_map ? (w.nt1 + kXcds - 1) / kXcds : 0;
+    const uint32_t* thist = f.rev ? w.hist1 : nullptr;
+    // compact: 12-B records + the 1-B level-2 digit column; flagged: each record's level-1 position kept,
+    // tile-strided and stored from registers (pt1) or at its input index, and counted against the tile histogram
+    const decltype(&k_part_scatter1<true, false>) k =
+        f.pt1                       ? k_part_scatter1<true, false, true, kL1Items, true, true, true, true, true>
+        : f.cmp && f.fl             ? k_part_scatter1<true, false, true, kL1Items, true, true, true, true>
+        : f.cmp                     ? k_part_scatter1<true, false, true, kL1Items, true, true, false, true>
+        : f.fl && f.k16             ? k_part_scatter1<true, false, true, kL1Items, true, true, true>
+        : f.fl                      ? k_part_scatter1<true, false, false, kL1Items, true, false, true>
+        : cols.packed_in && f.k16   ? k_part_scatter1<true, true, true, kL1Items, true>
+        : cols.packed_in            ? k_part_scatter1<true, true, false, kL1Items, true>
+        : f.k16 && f.vec1           ? k_part_scatter1<true, false, true, kL1Items, true>
+        : f.k16                     ? k_part_scatter1<true, false, true>
+        : f.pk                      ? k_part_scatter1<true, false, false, kL1Items, true>
+                                    : k_part_scatter1<false, false, false, kL1Items, true>;
+    if (w.hotp)                 // the compact order-free form with hot buckets: their records go to p2 in this pass
+        k_part_scatter1<kL1Items><<<grid, kPThreads, 0, c->stream>>>(
+            cols.key, cols.lt, cols.rank, cols.val, w.tm1, w.jb, c->d_misc, c->cap, f.shift1, c->p_toff.p, c->p1_rec.p,
+            c->p1_kj.p, xper1, f.pf, thist, HotL1{w.hb, c->p_toffh.p, f.rev ? c->p_hist1h.p : nullptr, c->p2_rec.p});
+    else
+        k<<<grid, kPThreads, 0, c->stream>>>(
+            cols.key, cols.lt, cols.rank, cols.val, w.tm1, w.jb, c->d_misc, c->cap, f.shift1, c->p_toff.p, c->p1_rec.p,
+            c->p1_kj.p, xper1, f.pf, thist, f.fl ? c->f_pos1.p : nullptr, f.fl ? w.hist1 : nullptr, KeyMap{0u, 8u});
+    if (w.ph) ev_record(c, ev_window(1, true));
+    if (c->place_timed && w.first) HIPCHK(hipEventRecord(c->place_ev[1], c->stream));
+    return CRDT_OK;
+}
+
+// Level-2 histogram of nt2 tiles over level 1's key column k1 (the form's column: 1-B digits, 2-B keys, kj words).
+void launch_l2_hist(L2Hist kind, const void* k1, const TileMap& tm2, uint32_t nt2, const crdt_ctx* c, uint32_t* hist,
+                    hipStream_t s) {
+    const uint16_t* k16 = static_cast<const uint16_t*>(k1);
+    if (kind == kH2Digit8)                      // the compact form's 1-B level-2 digits
+        k_part_hist16w<256, kPTile2, true><<<nt2, 256, 0, s>>>(k16, tm2, 0, hist);
+    else if (kind == kH2Wide8K)                 // key bits [4, 20) in 2 B: the level-2 digit (bits [12, 20)) is
+        k_part_hist16w<256, kPTile2><<<nt2, 256, 0, s>>>(k16, tm2, kSBits - 4, hist);   // its high byte
+    else if (kind == kH2Wide)
+        k_part_hist16w<<<nt2, kHThreads, 0, s>>>(k16, tm2, kSBits - 4, hist);
+    else if (kind == kH2Key16)
+        k_part_hist<false, true><<<nt2, kHThreads, 0, s>>>(k1, tm2, 0, c->d_misc, c->cap, kSBits - 4, hist);
+    else
+        k_part_hist<false><<<nt2, kHThreads, 0, s>>>(k1, tm2, 0, c->d_misc, c->cap, kSBits, hist);
+}
+
+// The level-2 scatter that keeps no changeset order, over nt tiles: the list forms' (stable with exact counts, or
+// order-free), or the packed forms' (compact: the record moves as it is, its digit is the word's top byte; else by
+// its 2-B, 1-B-final or 4-B key column).
+void launch_scatter2(bool stable, bool pk, bool cmp, bool k16, bool k8, const void* irec, const void* ikj,
+                     const TileMap& tm2, uint32_t nt, const uint32_t* toff, void* orec, void* okj, bool xcd_map,
+                     const uint32_t* thist, hipStream_t s) {
+    const uint32_t grid = xcd_grid(nt, xcd_map), xper2 = xcd_map ? (nt + kXcds - 1) / kXcds : 0;
+    const auto k = stable ? k_part_scatter2<true, false> : !pk ? k_part_scatter2<false, false>
+                   : cmp ? k_part_scatter2<false, true, true, true, true, true> : k16 ? k_part_scatter2<false, true, true, true>
+                   : k8 ? k_part_scatter2<false, true, true> : k_part_scatter2<false, true>;
+    cmp = cmp && pk && !stable;
+    k<<<grid, kPThreads, 0, s>>>(irec, cmp ? nullptr : ikj, tm2, cmp ? 24 : k16 && pk && !stable ? kSBits - 4 : kSBits, toff,
+                                 orec, cmp ? nullptr : okj, xper2, thist, nullptr);
+}
+
+// One flag pass of k_flags_back over nt tiles (kStop: level 1, back to input order), in the form's variant.
+template <bool kStop, int kT>
+void launch_flags_back(FlagPass v, bool fx, const TileMap& tm, uint32_t nt, const uint32_t* hist, const uint32_t* toff,
+                       const uint16_t* pos, const uint8_t* fsrc, uint8_t* fdst, const Misc* misc, hipStream_t s) {
+    const uint32_t grid = xcd_grid(nt, fx), xper = fx ? (nt + kXcds - 1) / kXcds : 0;
+    const auto k = v == kFpWide ? k_flags_back<kStop, 6, kT, true> : v == kFpChk4 ? k_flags_back<kStop, 4, kT, false>
+                   : v == kFpChk6 ? k_flags_back<kStop, 6, kT, false> : k_flags_back<kStop, 0, kT, false>;
+    k<<<grid, 512, 0, s>>>(tm, hist, toff, pos, fsrc, fdst, misc, xper);
+}
+
+// One window's host plan (segment bounds, changesets, level-1 tile prefix, scan map), its upload, its buffers.
+int sorted_win_plan(crdt_ctx* c, const SortedForm& f, const Cols& cols, const Segs& sg, SortedWin& w) {
+    const uint32_t nseg = w.nseg;
+    const uint64_t nw = w.nw;
+    // (the pinned staging buffer is reused: the previous window's copy must have run)
+    if (!w.first) SYNCHK(c, c->stream);
+    const size_t u32_words = (2 * (size_t)nseg + 2) / 2;        // seg_j [nseg] + tb [nseg + 1]
+    const size_t words = 2 * (size_t)nseg + u32_words + 3;
+    HIPALLOC(c->h_pplan.ensure(words));
+    HIPALLOC(c->p_plan.ensure(words));
+    uint64_t* h_beg = c->h_pplan.p;
+    uint64_t* h_end = c->h_pplan.p + nseg;
+    uint32_t* h_sj = reinterpret_cast<uint32_t*>(c->h_pplan.p + 2 * (size_t)nseg);
+    uint32_t* tb = h_sj + nseg;
+    uint32_t nt1 = 0;
+    // level-1 tile (CRDT_L1_TILE, A/B): kPTile, whose level-1 histogram the scan counts; another size
+    // (a multiple of 1024) takes the histogram pass
+    const uint32_t l1t = !c->l1_tile ? l1_plan_tile(c) : c->l1_tile;
+    for (uint32_t s = 0; s <= nseg; ++s) {
+        tb[s] = nt1;
+        if (s < nseg) {
+            h_beg[s] = sg.beg[w.s0 + s];
+            h_end[s] = sg.end[w.s0 + s];
+            h_sj[s] = sg.j[w.s0 + s];
+            nt1 += (uint32_t)((h_end[s] - h_beg[s] + l1t - 1) / l1t);
+        }
+    }
+    const uint32_t nc1 = (nt1 + kChunkTiles - 1) / kChunkTiles;
+    const size_t tail = 2 * (size_t)nseg + u32_words;
+    uint32_t* sm_t = reinterpret_cast<uint32_t*>(c->h_pplan.p + tail);
+    sm_t[0] = 0; sm_t[1] = nt1;                                   // scan tbase {0, nt1}
+    uint32_t* sm_c = reinterpret_cast<uint32_t*>(c->h_pplan.p + tail + 1);
+    sm_c[0] = 0; sm_c[1] = nc1;                                   // scan cbase {0, nc1}
+    c->h_pplan.p[tail + 2] = 0;                                   // seg_pos {0}
+    HIPCHK(hipMemcpyAsync(c->p_plan.p, c->h_pplan.p, words * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+    const uint32_t nt2 = f.two ? (uint32_t)((nw + kPTile2 - 1) / kPTile2) + kDigits : 0;
+    const uint32_t nc2 = f.two ? (nt2 + kChunkTiles - 1) / kChunkTiles + kDigits : 0;
+    const uint32_t ntm = std::max(nt1, nt2), ncm = std::max(nc1, nc2);
+    HIPALLOC(c->p_hist.ensure((size_t)ntm * kDigits));
+    HIPALLOC(c->p_toff.ensure((size_t)ntm * kDigits));
+    HIPALLOC(c->p_part.ensure((size_t)ncm * kDigits));
+    HIPALLOC(c->p_choff.ensure((size_t)ncm * kDigits));
+    HIPALLOC(c->p_dstart1.ensure(kDigits + 1));
+    // the partition buffers hold this form's records: packed payloads 12 B (Rec12), key columns 2 B at
+    // level 1 (k16) and 1 B at level 2 (k8); the wide form 16 + 4 B
+    const size_t rec_units = (f.pk ? (3 * (size_t)nw + 3) / 4 : (size_t)nw) + kPartPad;      // u32x4
+    const size_t kj1_units = (f.k16 ? ((size_t)nw + 1) / 2 : (size_t)nw) + kPartPad;          // uint32
+    const size_t kj2_units = (f.k8 ? ((size_t)nw + 3) / 4 : (size_t)nw) + kPartPad;
+    // a placement trial (PlaceTune): candidate place_trial stands in as p1 for this call, every window
+    // of it (swapped back in place_finish); the candidates are taken by the warm-up merge, sized for its
+    // form and capped (place_take)
+    if (c->place_k > 1 && c->place_trial < 0 && !c->has_comm && w.first && !c->place_warm) {
+        c->place_warm = true;
+        place_take(c, rec_units, kj1_units);
+    }
+    if (c->place_k > 1 && c->place_trial >= 0 && c->place_trial < 2 * c->place_k && !c->has_comm && w.first &&
+        !c->place_timed) {
+        const int k = c->place_trial % c->place_k;
+        if (k) {                                  // (grown like p1 itself when this call holds more records)
+            HIPALLOC(c->pc_rec[k].ensure(rec_units));
+            HIPALLOC(c->pc_kj[k].ensure(kj1_units));
+            std::swap(c->p1_rec, c->pc_rec[k]);
+            std::swap(c->p1_kj, c->pc_kj[k]);
+        }
+        for (hipEvent_t& e : c->place_ev)
+            if (!e) HIPCHK(hipEventCreate(&e));
+        c->place_timed = true;
+    }
+    HIPALLOC(c->p1_rec.ensure(rec_units)); HIPALLOC(c->p1_kj.ensure(kj1_units));
+    const uint64_t* d_beg = c->p_plan.p;
+    const uint64_t* d_end = c->p_plan.p + nseg;
+    const uint32_t* d_sj = reinterpret_cast<const uint32_t*>(c->p_plan.p + 2 * (size_t)nseg);
+    const uint32_t* d_tb1 = d_sj + nseg;
+    HIPALLOC(c->p_tseg.ensure(ntm));
+    k_seg_index<<<std::min<uint32_t>(grid_for(nt1, 256), 4096), 256, 0, c->stream>>>(d_tb1, nseg, nt1, c->p_tseg.p);
+    if (f.two) HIPALLOC(c->p_l1beg.ensure(kDigits + 1));
+    w.nt1 = nt1; w.nc1 = nc1; w.nt2 = nt2; w.nc2 = nc2; w.rec_units = rec_units; w.kj2_units = kj2_units;
+    w.tm1 = TileMap{d_beg, d_end, d_tb1, c->p_tseg.p, d_sj, nseg, l1t};
+    w.sm1z = ScanMap{reinterpret_cast<const uint32_t*>(c->p_plan.p + tail),
+                     reinterpret_cast<const uint32_t*>(c->p_plan.p + tail + 1), c->p_plan.p + tail + 2, 1};
+    // level-1 histogram: counted by the scan or by k_part_hist
+    // (the same key map — not route_l1's owner-major one, ADVICE r4 — and the same tile boundaries)
+    w.h1 = c->hist1_fused && !c->hist1_routed && w.only && !cols.packed_in && cols.key == c->hist1_key &&
+           c->hist1_shift == f.shift1 && nt1 == c->plan_ptiles && l1t == l1_plan_tile(c);
+    w.hist1 = w.h1 ? c->p_hist1.p : c->p_hist.p;
+    // the hot bins the scan counted apart: the compact order-free form of two levels takes them as level-1
+    // digits of their own (HotL1); any other form gets them back in digit 0 first
+    w.hb = w.h1 ? c->hist1_hot : 0u;
+    w.hot_n = w.hb && f.pk ? std::min<uint64_t>(c->h_misc->hot_n, nw) : 0;   // (read with the frame)
+    w.hotp = w.hb && f.cmp && !f.ord && !f.em && f.two && !c->has_comm && w.hot_n * 100 >= (uint64_t)c->hot_share * nw;
+    w.ph = c->timing && w.first && !f.em;
+    return CRDT_OK;
+}
+
+// Level-1 histogram (the scan's, trimmed, or k_part_hist's) and scans; hot digits first, from position 0.
+int sorted_l1_scans(crdt_ctx* c, const SortedForm& f, const Cols& cols, const SortedWin& w) {
+    const uint32_t R = c->plan_R, nt1 = w.nt1, nc1 = w.nc1;
+    if (w.hb && !w.hotp) {
+        k_hot_fold<<<std::min<uint32_t>(nt1, 1024u), 64, 0, c->stream>>>(c->p_hist1.p, c->p_hist1h.p, nt1);
+        c->hist1_hot = 0;
+        c->hot_skip = c->hot_probe;
+    }
+    if (w.hotp) {
+        HIPALLOC(c->p_toffh.ensure((size_t)nt1 * kDigits));
+        HIPALLOC(c->p_dstarth.ensure(kDigits + 1));
+        HIPALLOC(c->p_l1begh.ensure(kDigits + 1));
+        HIPALLOC(c->p2_rec.ensure(w.rec_units));     // level 1 writes the hot records there
+        k_hist_trim<<<256, 256, 0, c->stream>>>(c->p_hist1h.p, c->d_ptb, R, c->d_misc);
+        k_scan_part<<<nc1, 256, 0, c->stream>>>(c->p_hist1h.p, w.sm1z, c->p_part.p);
+        k_scan_seg<<<1, 256, 0, c->stream>>>(c->p_part.p, w.sm1z, c->p_choff.p, c->p_dstarth.p, c->p_l1begh.p);
+        k_scan_tiles<<<nc1, 256, 0, c->stream>>>(c->p_hist1h.p, c->p_choff.p, w.sm1z, c->p_dstarth.p, c->p_toffh.p);
+    }
+    const ScanMap sm1 = w.hotp ? ScanMap{w.sm1z.tbase, w.sm1z.cbase, c->p_l1begh.p + kDigits, 1} : w.sm1z;
+    if (w.h1)
+        k_hist_trim<<<256, 256, 0, c->stream>>>(c->p_hist1.p, c->d_ptb, R, c->d_misc);
+    else
+        k_part_hist<true><<<nt1, kHThreads, 0, c->stream>>>(cols.key, w.tm1, w.jb, c->d_misc, c->cap, f.shift1, c->p_hist.p);
+    k_scan_part<<<nc1, 256, 0, c->stream>>>(w.hist1, sm1, c->p_part.p);
+    k_scan_seg<<<1, 256, 0, c->stream>>>(c->p_part.p, sm1, c->p_choff.p, c->p_dstart1.p, f.two ? c->p_l1beg.p : nullptr);
+    k_scan_tiles<<<nc1, 256, 0, c->stream>>>(w.hist1, c->p_choff.p, sm1, c->p_dstart1.p, c->p_toff.p);
+    return CRDT_OK;
+}
+
+// Level 2 (two-level tables): level-1 bucket by level-1 bucket, tiles that never straddle one.
+int sorted_level2(crdt_ctx* c, const SortedForm& f, SortedWin& w) {
+    const uint64_t nw = w.nw;
+    const uint32_t nt2 = w.nt2, nc2 = w.nc2, ts2 = f.ts2;
+    HIPALLOC(c->p_l2map.ensure(2 * (kDigits + 1)));
+    HIPALLOC(c->p_dstart2.ensure(kDigits * kDigits + 1));
+    HIPALLOC(c->p2_rec.ensure(w.rec_units)); HIPALLOC(c->p2_kj.ensure(w.kj2_units));
+    uint32_t* tb2 = c->p_l2map.p;
+    uint32_t* cb2 = c->p_l2map.p + kDigits + 1;
+    // (the flagged form keeps level 1's tile histogram and offsets for its flag pass: level 2
+    // counts into buffers of its own)
+    if (f.fl) {
+        HIPALLOC(c->f_hist2.ensure((size_t)nt2 * kDigits));
+        HIPALLOC(c->f_toff2.ensure((size_t)nt2 * kDigits));
+    }
+    uint32_t* h2p = f.fl ? c->f_hist2.p : c->p_hist.p;
+    uint32_t* t2p = f.fl ? c->f_toff2.p : c->p_toff.p;
+    k_l2_plan<<<1, 256, 0, c->stream>>>(c->p_l1beg.p, tb2, cb2, ts2);
+    k_seg_index<<<std::min<uint32_t>(grid_for(nt2, 256), 4096), 256, 0, c->stream>>>(tb2, kDigits, nt2, c->p_tseg.p);
+    const TileMap tm2{c->p_l1beg.p, c->p_l1beg.p + 1, tb2, c->p_tseg.p, nullptr, kDigits, ts2};
+    w.tm2 = tm2;
+    const ScanMap sm2{tb2, cb2, c->p_l1beg.p, kDigits};
+    launch_l2_hist(f.h2, c->p1_kj.p, tm2, nt2, c, h2p, c->stream);
+    k_scan_part<<<nc2, 256, 0, c->stream>>>(h2p, sm2, c->p_part.p);
+    k_scan_seg<<<kDigits, 256, 0, c->stream>>>(c->p_part.p, sm2, c->p_choff.p, c->p_dstart2.p, nullptr);
+    k_scan_tiles<<<nc2, 256, 0, c->stream>>>(h2p, c->p_choff.p, sm2, c->p_dstart2.p, t2p);
+    // the hot buckets were filled by level 1 at [0, hot total): level 2 saw them empty, all starting there
+    if (w.hotp) k_hot_starts<<<1, 256, 0, c->stream>>>(c->p_dstart2.p, c->p_dstarth.p, w.hb);
+    // (nt2 is an upper bound of the level-2 tiles; the real count is on the device)
+    // (the grid and the XCD-contiguous mapping from a tile bound for THIS tile size: a loose
+    // bound would leave the upper XCDs' ranges past the last tile, idle)
+    // (the hot records are not level 2's: the scan's count of them is of every changeset, so nw - hot_n
+    // still bounds the records level 2 holds)
+    const uint64_t nw2 = w.hotp ? nw - w.hot_n : nw;
+    const uint32_t nt2s = (uint32_t)((nw2 + ts2 - 1) / ts2) + kDigits;
+    if (f.ord) {         // changeset order kept in every final bucket; level-2 run offsets kept
+        if (f.fl) HIPALLOC(c->f_pos2.ensure(nw + 8));
+        const auto k = f.cmp ? k_part_scatter2_seg<true, true, true> : f.k16 ? k_part_scatter2_seg<true, true>
+                       : f.k8 ? k_part_scatter2_seg<true, false> : k_part_scatter2_seg<false, false>;
+        k<<<xcd_grid(nt2s, c->xcd_map), kPThreads, 0, c->stream>>>(
+            reinterpret_cast<const Rec12*>(c->p1_rec.p), f.cmp ? nullptr : c->p1_kj.p, tm2,
+            f.cmp ? 24 : f.k16 ? kSBits - 4 : kSBits, t2p, reinterpret_cast<Rec12*>(c->p2_rec.p),
+            f.cmp ? nullptr : c->p2_kj.p, c->xcd_map ? (nt2s + kXcds - 1) / kXcds : 0, (uint32_t)pack_jmask(f.pf),
+            f.fl ? c->f_pos2.p : nullptr, h2p);
+    } else
+        launch_scatter2(c->counts, f.pk, f.cmp, f.k16, f.k8, c->p1_rec.p, c->p1_kj.p, tm2, nt2s, t2p, c->p2_rec.p,
+                        c->p2_kj.p, c->xcd_map, f.rev ? h2p : nullptr, c->stream);
+    return CRDT_OK;
+}
+
+// The resolve's items over the window's final buckets (k_bucket_items, k_seg_index) and its part-state buffers.
+int sorted_items(crdt_ctx* c, const SortedForm& f, const SortedWin& w, PackedItems& a) {
+    ItemGeom g = item_geom(f.two ? kDigits * kDigits : kDigits, w.nw);
+    HIPALLOC(c->p_ibase.ensure(g.ibase_units));
+    HIPALLOC(c->p_kslt.ensure(2 * g.ksn));
+    HIPALLOC(c->p_ksu32.ensure(6 * g.ksn));
+    g.bind(c->p_ibase.p);
+    HIPALLOC(c->p_ibucket.ensure(g.max_items));
+    a = PackedItems{f.two ? c->p_dstart2.p : c->p_dstart1.p, g, c->p_ibucket.p,
+                    reinterpret_cast<const Rec12*>(f.two ? c->p2_rec.p : c->p1_rec.p),
+                    f.two ? c->p2_kj.p : c->p1_kj.p, c->table, c->cap,
+                    c->d_Rj.p, reinterpret_cast<uint64_t*>(c->p_kslt.p), c->p_ksu32.p, f.pf, c->d_misc};
+    if (w.ph) ev_record(c, ev_window(3, false));
+    if (f.em) HIPALLOC(c->e_bbase.ensure(g.nb));
+    k_bucket_items<<<(g.nb + 1023) / 1024, 1024, 0, c->stream>>>(a.bst, g.nb, g.ib, g.hb, g.hot, c->d_misc,
+                                                               f.em ? c->e_bbase.p : nullptr);
+    k_seg_index<<<std::min<uint32_t>(grid_for(g.max_items, 256), 4096), 256, 0, c->stream>>>(g.ib, g.nb, g.max_items,
+                                                                                           c->p_ibucket.p);
+    return CRDT_OK;
+}
+
+// k_item_lists, then the host's wait for its counts (by then the GPU is at the resolve; the launches follow at once).
+struct ItemCounts { uint32_t fold, dense, sparse, hot, items; };
+int sorted_item_lists(crdt_ctx* c, const PackedItems& a, uint64_t hw_s, uint32_t sparse_s, ItemCounts* n) {
+    const ItemGeom& g = a.g;
+    HIPALLOC(c->p_ilist.ensure(kListHead + 3 * (size_t)g.max_items));
+    HIPALLOC(c->h_ilist.ensure(kListHead));
+    k_item_lists<<<(g.nb + 1023) / 1024, 1024, 0, c->stream>>>(a.bst, g.nb, g.ib, g.hb, g.hot, hw_s, sparse_s,
+                                                              c->p_ilist.p, g.max_items);
+    HIPCHK(hipMemcpyAsync(c->h_ilist.p, c->p_ilist.p, kListHead * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    const uint32_t* h = c->h_ilist.p;
+    if (h[0] > g.max_items || h[1] > g.max_items || h[2] > g.max_items || h[3] > g.max_hot || h[4] > g.max_items)
+        return CRDT_E_HIP;                              // (cannot happen: the lists hold <= max_items)
+    *n = ItemCounts{h[0], h[1], h[2], h[3], h[4]};
+    return CRDT_OK;
+}
+
+// Map-side combine: part folds, then every key's maximum emitted.
+int sorted_resolve_emit(crdt_ctx* c, const SortedForm& f, const SortedWin& w, const PackedItems& a, EmitOut* emit) {
+    const ItemGeom& g = a.g;
+    // emit items: the resolve's max_items, then 16 carry blocks per hot bucket; the slots are the
+    // buckets' (k_bucket_items' ebase: min(kSKeys, records) each), so at most min(records, key range)
+    const uint32_t n_items = g.max_items + g.max_hot * (kSKeys / 256);
+    const size_t slots = (size_t)std::min<uint64_t>(w.nw, (uint64_t)g.nb * kSKeys) + 1;
+    HIPALLOC(c->e_key.ensure(slots));
+    HIPALLOC(c->e_pk.ensure(slots));
+    HIPALLOC(c->e_val.ensure(slots));
+    HIPALLOC(c->e_icnt.ensure((size_t)n_items * (2 + emit->G)));
+    HIPCHK(hipMemsetAsync(c->e_icnt.p, 0, (size_t)n_items * (2 + emit->G) * sizeof(uint32_t), c->stream));
+    emit->key = c->e_key.p; emit->pk = c->e_pk.p; emit->val = c->e_val.p; emit->bbase = c->e_bbase.p;
+    emit->icount = c->e_icnt.p; emit->ibase = c->e_icnt.p + n_items; emit->ocount = c->e_icnt.p + 2 * (size_t)n_items;
+    emit->item0 = g.max_items; emit->n_items = n_items;
+    launch_packed_fold(a, f.cmp, f.k8, g.max_items, c->stream, 0, w.jb, nullptr);
+    launch_packed_emit(a, f.cmp, f.k8, g.max_items, c->stream, w.jb, *emit);
+    k_part_carry_packed<true><<<dim3(kSKeys / 256, g.max_hot), 256, 0, c->stream>>>(
+        g.hot, g.ib, g.hb, c->table, c->cap, 0, a.ps_key, a.ps_val, c->d_Rj.p, w.jb, f.pf, c->d_misc, *emit);
+    return CRDT_OK;
+}
+
+// The ordered packed resolve: flags and / or counts (sorted_path.inc, "win flags").  The split buckets' part folds
+// and carry-ins (ov: on the side stream, beside the unsplit buckets' walk: disjoint buckets), then their walk; the
+// fold and the carry-ins on exactly their items (k_item_lists), the walk on the items there are.
+int sorted_resolve_ordered(crdt_ctx* c, const SortedForm& f, const SortedWin& w, const PackedItems& a) {
+    const ItemGeom& g = a.g;
+    HIPALLOC(c->f_cin_key.ensure(g.ksn));
+    HIPALLOC(c->f_cin_val.ensure(g.ksn));
+    HIPALLOC(c->f_cin_pres.ensure(g.ksn));
+    if (f.fl) HIPALLOC(c->f_flag2.ensure(w.nw + 8));
+    uint8_t* fl2 = f.fl ? c->f_flag2.p : nullptr;
+    int st = CRDT_OK;
+    ItemCounts n{g.max_items, 0, 0, g.max_hot, g.max_items};
+    const uint32_t* l_fold = nullptr;
+    if (f.lists) {
+        if ((st = sorted_item_lists(c, a, 0, 0, &n))) return st;
+        l_fold = c->p_ilist.p + kListHead;
+    }
+    if ((st = f.ov ? overlap_fork(c) : CRDT_OK)) return st;
+    const hipStream_t fs = f.ov ? c->sstream : c->stream;
+    if (n.fold) launch_packed_fold(a, f.cmp, f.k8, n.fold, fs, c->hw_read, w.jb, l_fold);
+    if (n.hot)
+        k_part_cin_packed<<<dim3(kSKeys / 256, n.hot), 256, 0, fs>>>(
+            g.hot, g.ib, g.hb, c->table, c->cap, c->hw_read, a.ps_key, a.ps_val, f.pf, c->d_misc,
+            reinterpret_cast<uint64_t*>(c->f_cin_key.p), c->f_cin_val.p, c->f_cin_pres.p);
+    const uint64_t* cink = reinterpret_cast<const uint64_t*>(c->f_cin_key.p);
+    const auto walk = f.cmp ? k_resolve_pflags<false, true> : f.k8 ? k_resolve_pflags<true> : k_resolve_pflags<false>;
+    for (uint32_t which = f.ov ? 1u : 0u; which <= (f.ov ? 2u : 0u); ++which) {
+        if (which == 2 && (st = overlap_join(c))) return st;
+        if (n.items)
+            walk<<<n.items, kRThreads, 0, c->stream>>>(
+                a.bst, g.ib, g.hb, a.ibucket, g.nb, a.rec, f.cmp ? nullptr : a.kj, c->table, c->cap, c->hw_read, c->d_Rj.p,
+                w.jb, cink, c->f_cin_val.p, c->f_cin_pres.p, f.pf, c->d_misc, fl2, which);
+    }
+    return CRDT_OK;
+}
+
+// Flags back: level-2 order -> level-1 order (two levels) -> input order.
+int sorted_flags_back(crdt_ctx* c, const SortedForm& f, const SortedWin& w, uint8_t* dflags) {
+    const uint8_t* f1 = c->f_flag2.p;
+    if (f.two) {
+        HIPALLOC(c->f_flag1.ensure(w.nw + 8));
+        // (the flagged level 2 counted into f_hist2 / f_toff2; the grid from a tile bound for this tile size)
+        const uint32_t nt2f = (uint32_t)((w.nw + f.ts2 - 1) / f.ts2) + kDigits;
+        const uint32_t *h2 = c->f_hist2.p, *t2 = c->f_toff2.p;
+        if (f.fp2 == kFpPre)
+            (f.fp2_512 ? k_flags_back_pre<false, 6, kPTile2, 16> : k_flags_back_pre<false, 6, kPTile2, 32, 256>)
+                <<<nt2f, f.fp2_512 ? 512 : 256, 0, c->stream>>>(w.tm2, h2, t2, c->f_pos2.p, c->f_flag2.p, c->f_flag1.p,
+                                                                c->d_misc);
+        else
+            (f.ts2 == (uint32_t)kPTile2 ? launch_flags_back<false, kPTile2> : launch_flags_back<false, kPTile>)(
+                f.fp2, f.fback_xcd, w.tm2, nt2f, h2, t2, c->f_pos2.p, c->f_flag2.p, c->f_flag1.p, c->d_misc, c->stream);
+        f1 = c->f_flag1.p;
+        // level 2 reused the tile -> segment index: rebuild level 1's
+        k_seg_index<<<std::min<uint32_t>(grid_for(w.nt1, 256), 4096), 256, 0, c->stream>>>(w.tm1.tbase, w.nseg, w.nt1,
+                                                                                          c->p_tseg.p);
+    }
+    if (f.pt1 || f.fp1 == kFpPre)     // (pt1: the positions tile-strided)
+        (f.pt1 ? k_flags_back_pre<true, 6, kPTile, 14, 512, true> : k_flags_back_pre<true, 6, kPTile, 14>)
+            <<<w.nt1, 512, 0, c->stream>>>(w.tm1, w.hist1, c->p_toff.p, c->f_pos1.p, f1, dflags, c->d_misc);
+    else
+        launch_flags_back<true, kPTile>(f.fp1, f.fback_xcd, w.tm1, w.nt1, w.hist1, c->p_toff.p, c->f_pos1.p, f1, dflags,
+                                        c->d_misc, c->stream);
+    return CRDT_OK;
+}
+
+// The list forms (wide payloads): parts folded, carried, then every item from its carry-in; exact counts or order-free.
+template <bool kFree>
+void sorted_resolve_lists(crdt_ctx* c, const SortedWin& w, const PackedItems& a) {
+    const ItemGeom& g = a.g;
+    const u32x4* rec = reinterpret_cast<const u32x4*>(a.rec);
+    const uint32_t* rv = static_cast<const uint32_t*>(a.kj);
+    KeyState ps{c->p_kslt.p, c->p_ksu32.p, c->p_ksu32.p + g.ksn, c->p_ksu32.p + 2 * g.ksn};
+    KeyState cy{c->p_kslt.p + g.ksn, c->p_ksu32.p + 3 * g.ksn, c->p_ksu32.p + 4 * g.ksn, c->p_ksu32.p + 5 * g.ksn};
+    k_resolve<true, kFree><<<g.max_items, kRThreads, 0, c->stream>>>(a.bst, g.ib, g.hb, a.ibucket, g.nb, rec, rv, c->table,
+                                                                    c->cap, c->d_Rj.p, w.jb, ps, cy, c->d_misc);
+    k_part_carry<kFree><<<dim3(kSKeys / 256, g.max_hot), 256, 0, c->stream>>>(g.hot, g.ib, g.hb, c->table, c->cap, ps, cy,
+                                                                             c->d_Rj.p, w.jb, c->d_misc);
+    k_resolve<false, kFree><<<g.max_items, kRThreads, 0, c->stream>>>(a.bst, g.ib, g.hb, a.ibucket, g.nb, rec, rv, c->table,
+                                                                     c->cap, c->d_Rj.p, w.jb, ps, cy, c->d_misc);
+}
+
+// The packed order-free form: one LDS 64-bit max per record.  The split buckets' part folds + carry (ov: on the side
+// stream, beside the unsplit buckets' resolve: other rows, joined before the next window); the sparse buckets in
+// k_resolve_sparse's small workgroups (the dense ones skip them); each kernel on exactly its items (k_item_lists).
+int sorted_resolve_packed(crdt_ctx* c, const SortedForm& f, const SortedWin& w, const PackedItems& a) {
+    const ItemGeom& g = a.g;
+    int st = CRDT_OK;
+    ItemCounts n{g.max_items, g.max_items, g.max_items, g.max_hot, 0};
+    const uint32_t *l_fold = nullptr, *l_dense = nullptr, *l_sparse = nullptr;
+    if (f.lists) {
+        if ((st = sorted_item_lists(c, a, f.spk ? c->hw_read : 0, f.spk ? c->sparse_t : 0, &n))) return st;
+        l_fold = c->p_ilist.p + kListHead;
+        l_dense = l_fold + g.max_items;
+        l_sparse = l_dense + g.max_items;
+    }
+    if ((st = f.ov ? overlap_fork(c) : CRDT_OK)) return st;
+    const hipStream_t fs = f.ov ? c->sstream : c->stream;
+    if (n.fold) launch_packed_fold(a, f.cmp, f.k8, n.fold, fs, c->hw_read, w.jb, l_fold);
+    if (n.hot)
+        k_part_carry_packed<false><<<dim3(kSKeys / 256, n.hot), 256, 0, fs>>>(
+            g.hot, g.ib, g.hb, c->table, c->cap, c->hw_read, a.ps_key, a.ps_val, c->d_Rj.p, w.jb, f.pf, c->d_misc);
+    if (n.dense)
+        launch_packed_dense(a, f.cmp, f.k8, f.whole_lines, n.dense, c->stream, c->hw_read, w.jb, l_dense, c->sparse_t, f.spk);
+    if (f.spk && n.sparse) {
+        const auto k = f.cmp ? k_resolve_sparse<false, true> : f.k8 ? k_resolve_sparse<true, false>
+                                                                     : k_resolve_sparse<false, false>;
+        k<<<n.sparse, kSpThreads, 0, c->stream>>>(a.bst, g.ib, a.ibucket, g.nb, a.rec, f.cmp ? nullptr : a.kj, c->table,
+                                                  c->hw_read, c->d_Rj.p, w.jb, f.pf, c->d_misc, c->sparse_t, l_sparse);
+    }
+    if (f.ov && (st = overlap_join(c))) return st;
+    return CRDT_OK;
+}
+
+// One window: plan, level 1, level 2, the form's resolve, flags back.
+int sorted_window(crdt_ctx* c, const SortedForm& f, const Cols& cols, const Segs& sg, SortedWin& w, uint8_t* dflags,
+                  EmitOut* emit) {
+    int st;
+    if ((st = sorted_win_plan(c, f, cols, sg, w))) return st;
+    c->last_hist1_fused = w.h1; c->last_hot_direct = w.hotp;   // (the rest of the plan: sorted_form)
+    if ((st = sorted_l1_scans(c, f, cols, w))) return st;
+    if ((st = sorted_l1_scatter(c, f, cols, w))) return st;
+    if (w.ph) ev_record(c, ev_window(2, false));
+    if (f.two && (st = sorted_level2(c, f, w))) return st;
+    if (w.ph) ev_record(c, ev_window(2, true));
+    PackedItems a;
+    if ((st = sorted_items(c, f, w, a))) return st;
+    if (f.em)
+        st = sorted_resolve_emit(c, f, w, a, emit);
+    else if (f.ord)
+        st = sorted_resolve_ordered(c, f, w, a);
+    else if (c->counts)
+        sorted_resolve_lists<false>(c, w, a);
+    else if (f.pk)
+        st = sorted_resolve_packed(c, f, w, a);
+    else
+        sorted_resolve_lists<true>(c, w, a);
+    if (st) return st;
+    if (f.fl && (st = sorted_flags_back(c, f, w, dflags))) return st;
+    if (w.ph) {
+        ev_record(c, ev_window(3, true));
+        c->sorted_phases = true;
+        c->p1_records = w.nw;
+    }
+    HIPCHK(hipGetLastError());
+    // the next window reads rows this one may have written anywhere below the capacity
+    c->hw_read = c->cap;
+    return CRDT_OK;
+}
+
+// Sorted path (sorted_path.inc) for the whole batch: k_resolve (stop point), then per window of kWindow changesets a
+// level-1 (+ level-2) partition of the applied records and the per-bucket LDS resolve.  sg = the batch's changeset
+// segments (host), in changeset order; one changeset may be several segments (records routed in from several ranks).
+// dflags (device, zeroed by the caller): the flagged form; emit: the map-side combine (no row, result or timing).
 int apply_sorted(crdt_ctx* c, const Cols& cols, const Segs& sg, int64_t wall, const long long* d_event,
-                 crdt_result* out, uint8_t* dflags = nullptr,
-                 EmitOut* emit = nullptr) {
-    const uint32_t R = c->plan_R;
-    // dflags (device, zeroed by the caller): the flagged form — packed records, stable level 2, the
-    // ordered resolve with per-record flags, and the flags carried back to input order
-    const bool fl = dflags != nullptr;
-    // emit (comm_path.inc, map-side combine): fold the records against an absent table (the caller sets
-    // the key range and hw_read = 0) and emit one packed maximum per key; no row, result or timing
-    const bool em = emit != nullptr;
+                 crdt_result* out, uint8_t* dflags = nullptr, EmitOut* emit = nullptr) {
+    const bool fl = dflags != nullptr, em = emit != nullptr;
     if (!em) {
         if (!c->resolved)
-            k_resolve<<<1, 64, 0, c->stream>>>(d_event, R, wall, c->canonical, c->d_Rj.p, c->d_Cj.p, c->d_misc);
+            k_resolve<<<1, 64, 0, c->stream>>>(d_event, c->plan_R, wall, c->canonical, c->d_Rj.p, c->d_Cj.p, c->d_misc);
         c->resolved = false;
         ev_record(c, kEvApply);
         c->windows.clear();
         c->apply_total = 1;
         if (c->timing) ev_record(c, ev_window(0, false));
     }
-    const bool two = c->cap > (1ull << 20);
-    const uint32_t shift1 = two ? 20u : (uint32_t)kSBits;
-    const size_t ns_all = sg.j.size();
-    // order-free form: packed 12-B payloads and the packed resolve when the scan's frame of the
-    // batch fits the 64-bit key (one read-back of Misc per call), else wide payloads + lists
-    PackFrame pf{};
-    bool pk = false;
-    if (cols.packed_in || (c->packed_resolve && c->frame_on)) {
-        HIPCHK(hipMemcpyAsync(c->h_misc, c->d_misc, sizeof(Misc), hipMemcpyDeviceToHost, c->stream));
-        SYNCHK(c, c->stream);
-        pf = frame_of(c);
-        pk = pf.ok;
-        if (cols.packed_in && !pk) return CRDT_E_INVALID;           // routed packed under this same frame
-    }
-    if ((fl || em) && (!pk || cols.packed_in)) return CRDT_E_INVALID;   // the callers checked the frame
-    // the ordered packed form: the flagged form's kernels, for win flags and / or exact per-record
-    // counts (without flags: no positions kept, no flags carried back)
-    const bool ord = !em && (fl || (c->counts && pk && !cols.packed_in));
-    c->last_ordered = ord;
-    c->last_packed = pk;
-    c->key_end_valid = true;                 // k_bucket_items bounds the rows every window writes
-    c->last_hist1_fused = false;
-    c->last_hot_direct = false;
+    SortedForm f;
+    int st = sorted_form(c, cols, sg, fl, em, &f);
+    if (st) return st;
     c->sorted_phases = false;
-    // final records with a 1-B key column when the packed key leaves 4 bits free (two levels)
-    const bool k8 = pk && two && pf.key4 && !(c->form_off & kFormNoKey8);
-    const bool k16 = k8 && !(c->form_off & kFormNoKey16);     // ... and 2-B level-1 key columns
-    // the compact form (round 6; sorted_path.inc PackFrame::cb): on one ctx's order-free packed form, when the
-    // records' lt & 0xFFFF (the scan's fr_cmax) leave the lt field short enough, 12-B records that carry their
-    // whole 20-bit level-1 slot (+ a 1-B level-2 digit column at level 1) instead of 14 + 13 B
-    bool cmp = false;
-    if (k16 && (ord || !c->counts) && !em && !c->has_comm && !cols.packed_in && c->frame_on &&
-        !(c->form_off & (kFormNoCompact | kFormNoHistW | kFormBigTile2 | kFormNoWholeLines | kFormNoVecLoads))) {
-        const PackFrame cf = compact_frame(pf, (uint32_t)std::min<unsigned long long>(c->h_misc->fr_cmax, 0xFFFFull),
-                                           c->plan_R);
-        if (cf.cb) {
-            pf = cf;
-            cmp = true;
-        }
-    }
-    c->last_compact = cmp;
-    c->last_key8 = k8;
-    c->last_key16 = k16;
-    c->last_hw = pk && (!c->counts || ord) && c->hw_read < c->cap;     // (in the first window)
-    // flagged, compact, one window, the default level-1 flag pass: the level-1 positions tile-strided (kPT)
-    const uint32_t win0 = pk ? pf.jwin : kWindow;
-    const bool pt1 = fl && cmp && ns_all && sg.j[0] / win0 == sg.j[ns_all - 1] / win0 &&
-                     !(c->form_off & (kFormNoPosT | kFormNoFbackPre | kFormFbackWide)) &&
-                     !(c->xcd_map && (c->form_off & kFormFbackXcd));
-    if (fl && !pt1) {
+    const size_t ns_all = sg.j.size();
+    if (fl && !f.pt1) {
         uint64_t ncol = 0;                                           // input index space of pos1
         for (size_t s = 0; s < ns_all; ++s) ncol = std::max<uint64_t>(ncol, sg.end[s]);
         HIPALLOC(c->f_pos1.ensure((ncol ? ncol : 1) + 8));   // + 8: k_flags_back_pre's clamped loads
     }
     for (size_t sb = 0; sb < ns_all;) {
         // window [jb, jb + win): kWindow changesets (the kj word's field), the packed key's W
-        const uint32_t win = pk ? pf.jwin : kWindow;
-        const uint32_t jb = sg.j[sb] - sg.j[sb] % win;
+        SortedWin w;
+        w.jb = sg.j[sb] - sg.j[sb] % f.win;
         size_t se = sb;
-        uint64_t nw = 0;
-        while (se < ns_all && sg.j[se] < jb + win) { nw += sg.end[se] - sg.beg[se]; ++se; }
-        const uint32_t nseg = (uint32_t)(se - sb);
-        const size_t s0 = sb;
+        while (se < ns_all && sg.j[se] < w.jb + f.win) { w.nw += sg.end[se] - sg.beg[se]; ++se; }
+        w.nseg = (uint32_t)(se - sb);
+        w.s0 = sb;
+        w.first = sb == 0;
+        w.only = sb == 0 && se == ns_all;
         sb = se;
-        if (nw == 0) continue;
-        // host plan: segment bounds and changesets, level-1 tile prefix, the one-segment scan map
-        // (the pinned staging buffer is reused: the previous window's copy must have run)
-        if (s0 > 0) SYNCHK(c, c->stream);
-        const size_t u32_words = (2 * (size_t)nseg + 2) / 2;        // seg_j [nseg] + tb [nseg + 1]
-        const size_t words = 2 * (size_t)nseg + u32_words + 3;
-        HIPALLOC(c->h_pplan.ensure(words));
-        HIPALLOC(c->p_plan.ensure(words));
-        uint64_t* h_beg = c->h_pplan.p;
-        uint64_t* h_end = c->h_pplan.p + nseg;
-        uint32_t* h_sj = reinterpret_cast<uint32_t*>(c->h_pplan.p + 2 * (size_t)nseg);
-        uint32_t* tb = h_sj + nseg;
-        uint32_t nt1 = 0;
-        // level-1 tile (CRDT_L1_TILE, A/B): kPTile, whose level-1 histogram the scan counts; another size
-        // (a multiple of 1024) takes the histogram pass
-        const uint32_t l1t = !c->l1_tile ? l1_plan_tile(c) : c->l1_tile;
-        for (uint32_t s = 0; s <= nseg; ++s) {
-            tb[s] = nt1;
-            if (s < nseg) {
-                h_beg[s] = sg.beg[s0 + s];
-                h_end[s] = sg.end[s0 + s];
-                h_sj[s] = sg.j[s0 + s];
-                nt1 += (uint32_t)((h_end[s] - h_beg[s] + l1t - 1) / l1t);
-            }
-        }
-        const uint32_t nc1 = (nt1 + kChunkTiles - 1) / kChunkTiles;
-        const size_t tail = 2 * (size_t)nseg + u32_words;
-        uint32_t* sm_t = reinterpret_cast<uint32_t*>(c->h_pplan.p + tail);
-        sm_t[0] = 0; sm_t[1] = nt1;                                   // scan tbase {0, nt1}
-        uint32_t* sm_c = reinterpret_cast<uint32_t*>(c->h_pplan.p + tail + 1);
-        sm_c[0] = 0; sm_c[1] = nc1;                                   // scan cbase {0, nc1}
-        c->h_pplan.p[tail + 2] = 0;                                   // seg_pos {0}
-        HIPCHK(hipMemcpyAsync(c->p_plan.p, c->h_pplan.p, words * sizeof(uint64_t), hipMemcpyHostToDevice,
-                              c->stream));
-        const uint32_t nt2 = two ? (uint32_t)((nw + kPTile2 - 1) / kPTile2) + kDigits : 0;
-        const uint32_t nc2 = two ? (nt2 + kChunkTiles - 1) / kChunkTiles + kDigits : 0;
-        const uint32_t ntm = std::max(nt1, nt2), ncm = std::max(nc1, nc2);
-        HIPALLOC(c->p_hist.ensure((size_t)ntm * kDigits));
-        HIPALLOC(c->p_toff.ensure((size_t)ntm * kDigits));
-        HIPALLOC(c->p_part.ensure((size_t)ncm * kDigits));
-        HIPALLOC(c->p_choff.ensure((size_t)ncm * kDigits));
-        HIPALLOC(c->p_dstart1.ensure(kDigits + 1));
-        // the partition buffers hold this form's records: packed payloads 12 B (Rec12), key columns 2 B at
-        // level 1 (k16) and 1 B at level 2 (k8); the wide form 16 + 4 B
-        const size_t rec_units = (pk ? (3 * (size_t)nw + 3) / 4 : (size_t)nw) + kPartPad;      // u32x4
-        const size_t kj1_units = (k16 ? ((size_t)nw + 1) / 2 : (size_t)nw) + kPartPad;          // uint32
-        const size_t kj2_units = (k8 ? ((size_t)nw + 3) / 4 : (size_t)nw) + kPartPad;
-        // a placement trial (PlaceTune): candidate place_trial stands in as p1 for this call, every window
-        // of it (swapped back in place_finish); the candidates are taken by the warm-up merge, sized for its
-        // form and capped (place_take)
-        if (c->place_k > 1 && c->place_trial < 0 && !c->has_comm && s0 == 0 && !c->place_warm) {
-            c->place_warm = true;
-            place_take(c, rec_units, kj1_units);
-        }
-        if (c->place_k > 1 && c->place_trial >= 0 && c->place_trial < 2 * c->place_k && !c->has_comm && s0 == 0 &&
-            !c->place_timed) {
-            const int k = c->place_trial % c->place_k;
-            if (k) {                                  // (grown like p1 itself when this call holds more records)
-                HIPALLOC(c->pc_rec[k].ensure(rec_units));
-                HIPALLOC(c->pc_kj[k].ensure(kj1_units));
-                std::swap(c->p1_rec, c->pc_rec[k]);
-                std::swap(c->p1_kj, c->pc_kj[k]);
-            }
-            for (hipEvent_t& e : c->place_ev)
-                if (!e) HIPCHK(hipEventCreate(&e));
-            c->place_timed = true;
-        }
-        HIPALLOC(c->p1_rec.ensure(rec_units)); HIPALLOC(c->p1_kj.ensure(kj1_units));
-        u32x4* p1r = c->p1_rec.p;
-        uint32_t* p1k = c->p1_kj.p;
-        u32x4* p2r = nullptr;
-        uint32_t* p2k = nullptr;
-        const uint64_t* d_beg = c->p_plan.p;
-        const uint64_t* d_end = c->p_plan.p + nseg;
-        const uint32_t* d_sj = reinterpret_cast<const uint32_t*>(c->p_plan.p + 2 * (size_t)nseg);
-        const uint32_t* d_tb1 = d_sj + nseg;
-        HIPALLOC(c->p_tseg.ensure(ntm));
-        k_seg_index<<<std::min<uint32_t>(grid_for(nt1, 256), 4096), 256, 0, c->stream>>>(d_tb1, nseg, nt1, c->p_tseg.p);
-        const TileMap tm1{d_beg, d_end, d_tb1, c->p_tseg.p, d_sj, nseg, l1t};
-        const ScanMap sm1z{reinterpret_cast<const uint32_t*>(c->p_plan.p + tail),
-                          reinterpret_cast<const uint32_t*>(c->p_plan.p + tail + 1), c->p_plan.p + tail + 2, 1};
-        if (two) HIPALLOC(c->p_l1beg.ensure(kDigits + 1));
-        // level-1 histogram: counted by the scan (then only the changesets >= stop are cleared)
-        // or here
-        // (the same key map — not route_l1's owner-major one, ADVICE r4 — and the same tile boundaries)
-        const bool h1 = c->hist1_fused && !c->hist1_routed && s0 == 0 && se == ns_all && !cols.packed_in &&
-                        cols.key == c->hist1_key && c->hist1_shift == shift1 && nt1 == c->plan_ptiles &&
-                        l1t == l1_plan_tile(c);
-        const uint32_t* hist1 = h1 ? c->p_hist1.p : c->p_hist.p;
-        // the hot bins the scan counted apart: the compact order-free form of two levels takes them as level-1
-        // digits of their own (HotL1); any other form gets them back in digit 0 first
-        const uint32_t hb = h1 ? c->hist1_hot : 0u;
-        const uint64_t hot_n = hb && pk ? std::min<uint64_t>(c->h_misc->hot_n, nw) : 0;   // (read with the frame)
-        const bool hotp = hb && cmp && !ord && !em && two && !c->has_comm && hot_n * 100 >= (uint64_t)c->hot_share * nw;
-        if (hb && !hotp) {
-            k_hot_fold<<<std::min<uint32_t>(nt1, 1024u), 64, 0, c->stream>>>(c->p_hist1.p, c->p_hist1h.p, nt1);
-            c->hist1_hot = 0;
-            c->hot_skip = c->hot_probe;
-        }
-        c->last_hot_direct = hotp;
-        if (hotp) {       // hot digits first: their scan from position 0, then the ordinary one from the hot total
-            HIPALLOC(c->p_toffh.ensure((size_t)nt1 * kDigits));
-            HIPALLOC(c->p_dstarth.ensure(kDigits + 1));
-            HIPALLOC(c->p_l1begh.ensure(kDigits + 1));
-            HIPALLOC(c->p2_rec.ensure(rec_units));     // level 1 writes the hot records there
-            k_hist_trim<<<256, 256, 0, c->stream>>>(c->p_hist1h.p, c->d_ptb, R, c->d_misc);
-            k_scan_part<<<nc1, 256, 0, c->stream>>>(c->p_hist1h.p, sm1z, c->p_part.p);
-            k_scan_seg<<<1, 256, 0, c->stream>>>(c->p_part.p, sm1z, c->p_choff.p, c->p_dstarth.p, c->p_l1begh.p);
-            k_scan_tiles<<<nc1, 256, 0, c->stream>>>(c->p_hist1h.p, c->p_choff.p, sm1z, c->p_dstarth.p, c->p_toffh.p);
-        }
-        const ScanMap sm1 = hotp ? ScanMap{sm1z.tbase, sm1z.cbase, c->p_l1begh.p + kDigits, 1} : sm1z;
-        if (h1)
-            k_hist_trim<<<256, 256, 0, c->stream>>>(c->p_hist1.p, c->d_ptb, R, c->d_misc);
-        else
-            k_part_hist<true><<<nt1, kHThreads, 0, c->stream>>>(cols.key, tm1, jb, c->d_misc,
-                                                                 c->cap, shift1, c->p_hist.p);
-        c->last_hist1_fused = h1;
-        k_scan_part<<<nc1, 256, 0, c->stream>>>(hist1, sm1, c->p_part.p);
-        k_scan_seg<<<1, 256, 0, c->stream>>>(c->p_part.p, sm1, c->p_choff.p, c->p_dstart1.p,
-                                             two ? c->p_l1beg.p : nullptr);
-        k_scan_tiles<<<nc1, 256, 0, c->stream>>>(hist1, c->p_choff.p, sm1, c->p_dstart1.p, c->p_toff.p);
-        const bool ph = c->timing && s0 == 0 && !em;   // phase events: the first window
-        if (ph) ev_record(c, ev_window(1, false));
-        if (c->place_timed && s0 == 0) HIPCHK(hipEventRecord(c->place_ev[0], c->stream));   // (the first window)
-        const uint32_t xper1 = c->xcd_map ? (nt1 + kXcds - 1) / kXcds : 0;
-        const bool rev1 = c->xcd_map && !(c->form_off & kFormNoReverse);
-        if (pt1) HIPALLOC(c->f_pos1.ensure((size_t)nt1 * kPTile + 16));   // tile t's positions at t * kPTile
-        if (pt1)                // ... tile-strided, stored from registers
-            k_part_scatter1<true, false, true, kL1Items, true, true, true, true, true>
-                <<<xcd_grid(nt1, c->xcd_map), kPThreads, 0, c->stream>>>(
-                cols.key, cols.lt, cols.rank, cols.val, tm1, jb, c->d_misc, c->cap, shift1, c->p_toff.p, p1r,
-                p1k, xper1, pf, rev1 ? hist1 : nullptr, c->f_pos1.p, hist1);
-        else if (cmp && fl)     // the compact form's flagged level 1 (with positions)
-            k_part_scatter1<true, false, true, kL1Items, true, true, true, true>
-                <<<xcd_grid(nt1, c->xcd_map), kPThreads, 0, c->stream>>>(
-                cols.key, cols.lt, cols.rank, cols.val, tm1, jb, c->d_misc, c->cap, shift1, c->p_toff.p, p1r,
-                p1k, xper1, pf, rev1 ? hist1 : nullptr, c->f_pos1.p, hist1);
-        else if (hotp)          // the compact form with hot buckets: their records go to p2 in this pass
-            k_part_scatter1<kL1Items><<<xcd_grid(nt1, c->xcd_map), kPThreads, 0, c->stream>>>(
-                cols.key, cols.lt, cols.rank, cols.val, tm1, jb, c->d_misc, c->cap, shift1, c->p_toff.p, p1r,
-                p1k, xper1, pf, rev1 ? hist1 : nullptr,
-                HotL1{hb, c->p_toffh.p, rev1 ? c->p_hist1h.p : nullptr, c->p2_rec.p});
-        else if (cmp)           // the compact form: 12-B records + the 1-B level-2 digit column
-            k_part_scatter1<true, false, true, kL1Items, true, true, false, true>
-                <<<xcd_grid(nt1, c->xcd_map), kPThreads, 0, c->stream>>>(
-                cols.key, cols.lt, cols.rank, cols.val, tm1, jb, c->d_misc, c->cap, shift1, c->p_toff.p, p1r,
-                p1k, xper1, pf, rev1 ? hist1 : nullptr);
-        else if (fl && k16)     // the flagged form: each record's level-1 position kept at its input index
-            k_part_scatter1<true, false, true, kL1Items, true, true, true>
-                <<<xcd_grid(nt1, c->xcd_map), kPThreads, 0, c->stream>>>(
-                cols.key, cols.lt, cols.rank, cols.val, tm1, jb, c->d_misc, c->cap, shift1, c->p_toff.p, p1r,
-                p1k, xper1, pf, rev1 ? hist1 : nullptr, c->f_pos1.p, hist1);
-        else if (fl)
-            k_part_scatter1<true, false, false, kL1Items, true, false, true>
-                <<<xcd_grid(nt1, c->xcd_map), kPThreads, 0, c->stream>>>(
-                cols.key, cols.lt, cols.rank, cols.val, tm1, jb, c->d_misc, c->cap, shift1, c->p_toff.p, p1r,
-                p1k, xper1, pf, rev1 ? hist1 : nullptr, c->f_pos1.p, hist1);
-        else if (cols.packed_in && k16)
-            k_part_scatter1<true, true, true, kL1Items, true><<<xcd_grid(nt1, c->xcd_map), kPThreads, 0, c->stream>>>(
-                cols.key, cols.lt, cols.rank, cols.val, tm1, jb, c->d_misc, c->cap, shift1, c->p_toff.p, p1r,
-                p1k, xper1, pf, rev1 ? hist1 : nullptr);
-        else if (cols.packed_in)
-            k_part_scatter1<true, true, false, kL1Items, true><<<xcd_grid(nt1, c->xcd_map), kPThreads, 0, c->stream>>>(
-                cols.key, cols.lt, cols.rank, cols.val, tm1, jb, c->d_misc, c->cap, shift1, c->p_toff.p, p1r,
-                p1k, xper1, pf, rev1 ? hist1 : nullptr);
-        else if (k16 && !(c->form_off & kFormNoVecLoads))
-            k_part_scatter1<true, false, true, kL1Items, true><<<xcd_grid(nt1, c->xcd_map), kPThreads, 0, c->stream>>>(
-                cols.key, cols.lt, cols.rank, cols.val, tm1, jb, c->d_misc, c->cap, shift1, c->p_toff.p, p1r,
-                p1k, xper1, pf, rev1 ? hist1 : nullptr);
-        else if (k16)
-            k_part_scatter1<true, false, true><<<xcd_grid(nt1, c->xcd_map), kPThreads, 0, c->stream>>>(
-                cols.key, cols.lt, cols.rank, cols.val, tm1, jb, c->d_misc, c->cap, shift1, c->p_toff.p, p1r,
-                p1k, xper1, pf, rev1 ? hist1 : nullptr);
-        else if (pk)
-            k_part_scatter1<true, false, false, kL1Items, true><<<xcd_grid(nt1, c->xcd_map), kPThreads, 0, c->stream>>>(
-                cols.key, cols.lt, cols.rank, cols.val, tm1, jb, c->d_misc, c->cap, shift1, c->p_toff.p, p1r,
-                p1k, xper1, pf, rev1 ? hist1 : nullptr);
-        else
-            k_part_scatter1<false, false, false, kL1Items, true><<<xcd_grid(nt1, c->xcd_map), kPThreads, 0, c->stream>>>(
-                cols.key, cols.lt, cols.rank, cols.val, tm1, jb, c->d_misc, c->cap, shift1, c->p_toff.p, p1r,
-                p1k, xper1, pf, rev1 ? hist1 : nullptr);
-        if (ph) ev_record(c, ev_window(1, true));
-        if (c->place_timed && s0 == 0) HIPCHK(hipEventRecord(c->place_ev[1], c->stream));
-        if (ph) ev_record(c, ev_window(2, false));
-        TileMap tm2f{};                              // level 2's tiling and counts (the flag pass)
-        uint32_t nt2f = 0;
-        const uint32_t* h2f = nullptr;
-        const uint32_t* t2f = nullptr;
-        if (two) {
-            HIPALLOC(c->p_l2map.ensure(2 * (kDigits + 1)));
-            HIPALLOC(c->p_dstart2.ensure(kDigits * kDigits + 1));
-            HIPALLOC(c->p2_rec.ensure(rec_units)); HIPALLOC(c->p2_kj.ensure(kj2_units));
-            p2r = c->p2_rec.p;
-            p2k = c->p2_kj.p;
-            uint32_t* tb2 = c->p_l2map.p;
-            uint32_t* cb2 = c->p_l2map.p + kDigits + 1;
-            // level-2 tiles of the packed form: kPTile2 records (one sub-tile each) — 256 workgroups
-            // then cover a short stretch of each level-1 bucket at a time
-            const uint32_t ts2 = k16 && !(c->form_off & kFormNoHistW) && !(c->form_off & kFormBigTile2)
-                                 ? (uint32_t)kPTile2 : (uint32_t)kPTile;
-            // (the flagged form keeps level 1's tile histogram and offsets for its flag pass: level 2
-            // counts into buffers of its own)
-            if (fl) {
-                HIPALLOC(c->f_hist2.ensure((size_t)nt2 * kDigits));
-                HIPALLOC(c->f_toff2.ensure((size_t)nt2 * kDigits));
-            }
-            uint32_t* h2p = fl ? c->f_hist2.p : c->p_hist.p;
-            uint32_t* t2p = fl ? c->f_toff2.p : c->p_toff.p;
-            h2f = h2p;
-            t2f = t2p;
-            k_l2_plan<<<1, 256, 0, c->stream>>>(c->p_l1beg.p, tb2, cb2, ts2);
-            k_seg_index<<<std::min<uint32_t>(grid_for(nt2, 256), 4096), 256, 0, c->stream>>>(tb2, kDigits, nt2,
-                                                                                            c->p_tseg.p);
-            const TileMap tm2{c->p_l1beg.p, c->p_l1beg.p + 1, tb2, c->p_tseg.p, nullptr, kDigits, ts2};
-            tm2f = tm2;
-            nt2f = (uint32_t)((nw + ts2 - 1) / ts2) + kDigits;
-            const ScanMap sm2{tb2, cb2, c->p_l1beg.p, kDigits};
-            if (cmp)                                     // the compact form's 1-B level-2 digits
-                k_part_hist16w<256, kPTile2, true><<<nt2, 256, 0, c->stream>>>(
-                    reinterpret_cast<const uint16_t*>(p1k), tm2, 0, h2p);
-            else if (k16 && !(c->form_off & kFormNoHistW) && ts2 == (uint32_t)kPTile2)   // key bits [4, 20) in 2 B:
-                k_part_hist16w<256, kPTile2><<<nt2, 256, 0, c->stream>>>(   // the level-2 digit (bits [12, 20))
-                    reinterpret_cast<const uint16_t*>(p1k), tm2, kSBits - 4, h2p);   // is its high byte
-            else if (k16 && !(c->form_off & kFormNoHistW))
-                k_part_hist16w<<<nt2, kHThreads, 0, c->stream>>>(
-                    reinterpret_cast<const uint16_t*>(p1k), tm2, kSBits - 4, h2p);
-            else if (k16)
-                k_part_hist<false, true><<<nt2, kHThreads, 0, c->stream>>>(p1k, tm2, 0, c->d_misc, c->cap,
-                                                                          kSBits - 4, h2p);
-            else
-                k_part_hist<false><<<nt2, kHThreads, 0, c->stream>>>(p1k, tm2, 0, c->d_misc, c->cap, kSBits,
-                                                                      h2p);
-            k_scan_part<<<nc2, 256, 0, c->stream>>>(h2p, sm2, c->p_part.p);
-            k_scan_seg<<<kDigits, 256, 0, c->stream>>>(c->p_part.p, sm2, c->p_choff.p, c->p_dstart2.p, nullptr);
-            k_scan_tiles<<<nc2, 256, 0, c->stream>>>(h2p, c->p_choff.p, sm2, c->p_dstart2.p, t2p);
-            // the hot buckets were filled by level 1 at [0, hot total): level 2 saw them empty, all starting there
-            if (hotp) k_hot_starts<<<1, 256, 0, c->stream>>>(c->p_dstart2.p, c->p_dstarth.p, hb);
-            // (nt2 is an upper bound of the level-2 tiles; the real count is on the device)
-            // (the grid and the XCD-contiguous mapping from a tile bound for THIS tile size: a loose
-            // bound would leave the upper XCDs' ranges past the last tile, idle)
-            // (the hot records are not level 2's: the scan's count of them is of every changeset, so nw - hot_n
-            // still bounds the records level 2 holds)
-            const uint64_t nw2 = hotp ? nw - hot_n : nw;
-            const uint32_t nt2s = (uint32_t)((nw2 + ts2 - 1) / ts2) + kDigits;
-            const uint32_t xper2 = c->xcd_map ? (nt2s + kXcds - 1) / kXcds : 0;
-            if (ord) {         // changeset order kept in every final bucket; level-2 run offsets kept
-                if (fl) HIPALLOC(c->f_pos2.ensure(nw + 8));
-                uint16_t* pos2 = fl ? c->f_pos2.p : nullptr;
-                const Rec12* i12 = reinterpret_cast<const Rec12*>(p1r);
-                Rec12* o12 = reinterpret_cast<Rec12*>(p2r);
-                const uint32_t jm = (uint32_t)pack_jmask(pf);
-                if (cmp)
-                    k_part_scatter2_seg<true, true, true><<<xcd_grid(nt2s, c->xcd_map), kPThreads, 0, c->stream>>>(
-                        i12, nullptr, tm2, 24, t2p, o12, nullptr, xper2, jm, pos2, h2p);
-                else if (k16)
-                    k_part_scatter2_seg<true, true><<<xcd_grid(nt2s, c->xcd_map), kPThreads, 0, c->stream>>>(
-                        i12, p1k, tm2, kSBits - 4, t2p, o12, p2k, xper2, jm, pos2, h2p);
-                else if (k8)
-                    k_part_scatter2_seg<true, false><<<xcd_grid(nt2s, c->xcd_map), kPThreads, 0, c->stream>>>(
-                        i12, p1k, tm2, kSBits, t2p, o12, p2k, xper2, jm, pos2, h2p);
-                else
-                    k_part_scatter2_seg<false, false><<<xcd_grid(nt2s, c->xcd_map), kPThreads, 0, c->stream>>>(
-                        i12, p1k, tm2, kSBits, t2p, o12, p2k, xper2, jm, pos2, h2p);
-            } else if (c->counts)
-                k_part_scatter2<true, false><<<xcd_grid(nt2s, c->xcd_map), kPThreads, 0, c->stream>>>(
-                    p1r, p1k, tm2, kSBits, t2p, p2r, p2k, xper2, rev1 ? h2p : nullptr);
-            else if (pk)
-                if (cmp)       // (the record moves as it is: its digit is the word's top byte)
-                    k_part_scatter2<false, true, true, true, true, true>
-                        <<<xcd_grid(nt2s, c->xcd_map), kPThreads, 0, c->stream>>>(
-                        p1r, nullptr, tm2, 24, t2p, p2r, nullptr, xper2, rev1 ? h2p : nullptr);
-                else if (k16)
-                    k_part_scatter2<false, true, true, true><<<xcd_grid(nt2s, c->xcd_map), kPThreads, 0, c->stream>>>(
-                        p1r, p1k, tm2, kSBits - 4, t2p, p2r, p2k, xper2, rev1 ? h2p : nullptr);
-                else if (k8)
-                    k_part_scatter2<false, true, true><<<xcd_grid(nt2s, c->xcd_map), kPThreads, 0, c->stream>>>(
-                        p1r, p1k, tm2, kSBits, t2p, p2r, p2k, xper2, rev1 ? h2p : nullptr);
-                else
-                    k_part_scatter2<false, true><<<xcd_grid(nt2s, c->xcd_map), kPThreads, 0, c->stream>>>(
-                        p1r, p1k, tm2, kSBits, t2p, p2r, p2k, xper2, rev1 ? h2p : nullptr);
-            else
-                k_part_scatter2<false, false><<<xcd_grid(nt2s, c->xcd_map), kPThreads, 0, c->stream>>>(
-                    p1r, p1k, tm2, kSBits, t2p, p2r, p2k, xper2, rev1 ? h2p : nullptr);
-        }
-        if (ph) ev_record(c, ev_window(2, true));
-        // resolve: items = parts of buckets (hot buckets split into kRPart-record parts)
-        const uint32_t nb = two ? kDigits * kDigits : kDigits;
-        const uint32_t* bst = two ? c->p_dstart2.p : c->p_dstart1.p;
-        const u32x4* rec = two ? p2r : p1r;
-        const uint32_t* rv = two ? p2k : p1k;
-        const uint32_t max_items = nb + (uint32_t)(nw / kRPart) + 1;
-        const size_t ksn = (size_t)(2 * (nw / kRPart) + 2) * kSKeys;     // part-state slots of split buckets
-        const uint32_t max_hot = std::min<uint32_t>(nb, (uint32_t)(nw / kRPart) + 1);   // split buckets hold > kRPart
-        HIPALLOC(c->p_ibase.ensure(2 * (nb + 1) + 1 + max_hot));
-        HIPALLOC(c->p_kslt.ensure(2 * ksn));
-        HIPALLOC(c->p_ksu32.ensure(6 * ksn));
-        uint32_t* d_ib = c->p_ibase.p;
-        uint32_t* d_hb = c->p_ibase.p + nb + 1;
-        uint32_t* d_hot = c->p_ibase.p + 2 * (nb + 1);                           // [0] count, [1..] buckets
-        KeyState ps{c->p_kslt.p, c->p_ksu32.p, c->p_ksu32.p + ksn, c->p_ksu32.p + 2 * ksn};
-        KeyState cy{c->p_kslt.p + ksn, c->p_ksu32.p + 3 * ksn, c->p_ksu32.p + 4 * ksn, c->p_ksu32.p + 5 * ksn};
-        HIPALLOC(c->p_ibucket.ensure(max_items));
-        // split buckets (parts folded apart, then carried) beside the unsplit buckets' resolve: two streams
-        const bool ov = !em && pk && (ord || !c->counts) && two && (c->form_off & kFormOverlap);
-        if (ph) ev_record(c, ev_window(3, false));
-        if (em) HIPALLOC(c->e_bbase.ensure(nb));
-        k_bucket_items<<<(nb + 1023) / 1024, 1024, 0, c->stream>>>(bst, nb, d_ib, d_hb, d_hot, c->d_misc,
-                                                                    em ? c->e_bbase.p : nullptr);
-        k_seg_index<<<std::min<uint32_t>(grid_for(max_items, 256), 4096), 256, 0, c->stream>>>(d_ib, nb, max_items,
-                                                                                               c->p_ibucket.p);
-        // k_item_lists, then the host's wait for its counts (the packed resolve's kernels on exactly their items)
-        auto item_lists = [&](uint64_t hw_s, uint32_t sparse_s, uint32_t* n_fold, uint32_t* n_dense, uint32_t* n_sparse,
-                              uint32_t* n_hot, uint32_t* n_items) -> int {
-            HIPALLOC(c->p_ilist.ensure(kListHead + 3 * (size_t)max_items));
-            HIPALLOC(c->h_ilist.ensure(kListHead));
-            k_item_lists<<<(nb + 1023) / 1024, 1024, 0, c->stream>>>(bst, nb, d_ib, d_hb, d_hot, hw_s, sparse_s,
-                                                                    c->p_ilist.p, max_items);
-            HIPCHK(hipMemcpyAsync(c->h_ilist.p, c->p_ilist.p, kListHead * sizeof(uint32_t), hipMemcpyDeviceToHost,
-                                  c->stream));
-            HIPCHK(hipStreamSynchronize(c->stream));
-            const uint32_t* h = c->h_ilist.p;
-            if (h[0] > max_items || h[1] > max_items || h[2] > max_items || h[3] > max_hot || h[4] > max_items)
-                return CRDT_E_HIP;                              // (cannot happen: the lists hold <= max_items)
-            *n_fold = h[0]; *n_dense = h[1]; *n_sparse = h[2]; *n_hot = h[3]; *n_items = h[4];
-            return CRDT_OK;
-        };
-        if (em) {          // map-side combine: part folds, then every key's maximum emitted
-            // emit items: the resolve's max_items, then 16 carry blocks per hot bucket; the slots are the
-            // buckets' (k_bucket_items' ebase: min(kSKeys, records) each), so at most min(records, key range)
-            const uint32_t n_items = max_items + max_hot * (kSKeys / 256);
-            const size_t slots = (size_t)std::min<uint64_t>(nw, (uint64_t)nb * kSKeys) + 1;
-            HIPALLOC(c->e_key.ensure(slots));
-            HIPALLOC(c->e_pk.ensure(slots));
-            HIPALLOC(c->e_val.ensure(slots));
-            HIPALLOC(c->e_icnt.ensure((size_t)n_items * (2 + emit->G)));
-            HIPCHK(hipMemsetAsync(c->e_icnt.p, 0, (size_t)n_items * (2 + emit->G) * sizeof(uint32_t), c->stream));
-            emit->key = c->e_key.p;
-            emit->pk = c->e_pk.p;
-            emit->val = c->e_val.p;
-            emit->bbase = c->e_bbase.p;
-            emit->icount = c->e_icnt.p;
-            emit->ibase = c->e_icnt.p + n_items;
-            emit->ocount = c->e_icnt.p + 2 * (size_t)n_items;
-            emit->item0 = max_items;
-            emit->n_items = n_items;
-            uint64_t* ps_key = reinterpret_cast<uint64_t*>(c->p_kslt.p);
-            uint32_t* ps_val = c->p_ksu32.p;
-            const Rec12* rec12 = reinterpret_cast<const Rec12*>(rec);
-            if (k8) {
-                k_resolve_packed<true, true, true><<<max_items, kQThreads, 0, c->stream>>>(
-                    bst, d_ib, d_hb, c->p_ibucket.p, nb, rec12, rv, c->table, c->cap, 0, c->d_Rj.p, jb, ps_key, ps_val,
-                    pf, c->d_misc);
-                k_resolve_packed<false, false, true, true><<<max_items, kQThreads, 0, c->stream>>>(
-                    bst, d_ib, d_hb, c->p_ibucket.p, nb, rec12, rv, c->table, c->cap, 0, c->d_Rj.p, jb, ps_key, ps_val,
-                    pf, c->d_misc, *emit);
-            } else {
-                k_resolve_packed<true><<<max_items, kQThreads, 0, c->stream>>>(
-                    bst, d_ib, d_hb, c->p_ibucket.p, nb, rec12, rv, c->table, c->cap, 0, c->d_Rj.p, jb, ps_key, ps_val,
-                    pf, c->d_misc);
-                k_resolve_packed<false, false, false, true><<<max_items, kQThreads, 0, c->stream>>>(
-                    bst, d_ib, d_hb, c->p_ibucket.p, nb, rec12, rv, c->table, c->cap, 0, c->d_Rj.p, jb, ps_key, ps_val,
-                    pf, c->d_misc, *emit);
-            }
-            k_part_carry_packed<true><<<dim3(kSKeys / 256, max_hot), 256, 0, c->stream>>>(
-                d_hot, d_ib, d_hb, c->table, c->cap, 0, ps_key, ps_val, c->d_Rj.p, jb, pf, c->d_misc, *emit);
-        } else if (ord) {  // the ordered packed resolve: flags and / or counts (sorted_path.inc, "win flags")
-            uint64_t* ps_key = reinterpret_cast<uint64_t*>(c->p_kslt.p);
-            uint32_t* ps_val = c->p_ksu32.p;
-            const Rec12* rec12 = reinterpret_cast<const Rec12*>(rec);
-            HIPALLOC(c->f_cin_key.ensure(ksn));
-            HIPALLOC(c->f_cin_val.ensure(ksn));
-            HIPALLOC(c->f_cin_pres.ensure(ksn));
-            if (fl) HIPALLOC(c->f_flag2.ensure(nw + 8));
-            uint8_t* fl2 = fl ? c->f_flag2.p : nullptr;
-            // the split buckets' part folds and carry-ins on the side stream, beside the unsplit buckets' ordered
-            // resolve (disjoint buckets: their rows, states and flags do not meet); then the split buckets' walk
-            // the fold and the carry-ins on exactly their items (k_item_lists), the walk on the items there are
-            int st = CRDT_OK;
-            uint32_t g_fold = max_items, g_hot = max_hot, g_items = max_items, g_d, g_s;
-            const uint32_t* l_fold = nullptr;
-            if (!c->has_comm && !(c->form_off & kFormNoItemLists)) {
-                if ((st = item_lists(0, 0, &g_fold, &g_d, &g_s, &g_hot, &g_items))) return st;
-                l_fold = c->p_ilist.p + kListHead;
-            }
-            if ((st = ov ? overlap_fork(c) : CRDT_OK)) return st;
-            const hipStream_t fs = ov ? c->sstream : c->stream;
-            if (!g_fold) {
-            } else if (cmp)
-                k_resolve_packed<true, true, false, false, true><<<g_fold, kQThreads, 0, fs>>>(
-                    bst, d_ib, d_hb, c->p_ibucket.p, nb, rec12, nullptr, c->table, c->cap, c->hw_read, c->d_Rj.p, jb,
-                    ps_key, ps_val, pf, c->d_misc, EmitOut{}, 0, false, l_fold);
-            else if (k8)
-                k_resolve_packed<true, true, true><<<g_fold, kQThreads, 0, fs>>>(
-                    bst, d_ib, d_hb, c->p_ibucket.p, nb, rec12, rv, c->table, c->cap, c->hw_read, c->d_Rj.p, jb, ps_key,
-                    ps_val, pf, c->d_misc, EmitOut{}, 0, false, l_fold);
-            else
-                k_resolve_packed<true><<<g_fold, kQThreads, 0, fs>>>(
-                    bst, d_ib, d_hb, c->p_ibucket.p, nb, rec12, rv, c->table, c->cap, c->hw_read, c->d_Rj.p, jb, ps_key,
-                    ps_val, pf, c->d_misc, EmitOut{}, 0, false, l_fold);
-            if (g_hot)
-                k_part_cin_packed<<<dim3(kSKeys / 256, g_hot), 256, 0, fs>>>(
-                    d_hot, d_ib, d_hb, c->table, c->cap, c->hw_read, ps_key, ps_val, pf, c->d_misc,
-                    reinterpret_cast<uint64_t*>(c->f_cin_key.p), c->f_cin_val.p, c->f_cin_pres.p);
-            const uint64_t* cink = reinterpret_cast<const uint64_t*>(c->f_cin_key.p);
-            for (uint32_t which = ov ? 1u : 0u; which <= (ov ? 2u : 0u); ++which) {
-                if (which == 2 && (st = overlap_join(c))) return st;
-                if (!g_items) {
-                } else if (cmp)
-                    k_resolve_pflags<false, true><<<g_items, kRThreads, 0, c->stream>>>(
-                        bst, d_ib, d_hb, c->p_ibucket.p, nb, rec12, nullptr, c->table, c->cap, c->hw_read, c->d_Rj.p,
-                        jb, cink, c->f_cin_val.p, c->f_cin_pres.p, pf, c->d_misc, fl2, which);
-                else if (k8)
-                    k_resolve_pflags<true><<<g_items, kRThreads, 0, c->stream>>>(
-                        bst, d_ib, d_hb, c->p_ibucket.p, nb, rec12, rv, c->table, c->cap, c->hw_read, c->d_Rj.p, jb,
-                        cink, c->f_cin_val.p, c->f_cin_pres.p, pf, c->d_misc, fl2, which);
-                else
-                    k_resolve_pflags<false><<<g_items, kRThreads, 0, c->stream>>>(
-                        bst, d_ib, d_hb, c->p_ibucket.p, nb, rec12, rv, c->table, c->cap, c->hw_read, c->d_Rj.p, jb,
-                        cink, c->f_cin_val.p, c->f_cin_pres.p, pf, c->d_misc, fl2, which);
-            }
-            // flags back: level-2 order -> level-1 order (two levels) -> input order
-            const uint8_t* f1 = c->f_flag2.p;
-            if (fl && two) {
-                HIPALLOC(c->f_flag1.ensure(nw + 8));
-                const bool fx = c->xcd_map && (c->form_off & kFormFbackXcd);
-                const uint32_t xf2 = fx ? (nt2f + kXcds - 1) / kXcds : 0;
-#define CRDT_FBACK2(CHK, W)                                                                               \
-    if (tm2f.tsize == (uint32_t)kPTile2)                                                                  \
-        k_flags_back<false, CHK, kPTile2, W><<<xcd_grid(nt2f, fx), 512, 0, c->stream>>>(                  \
-            tm2f, h2f, t2f, c->f_pos2.p, c->f_flag2.p, c->f_flag1.p, c->d_misc, xf2);                     \
-    else                                                                                                  \
-        k_flags_back<false, CHK, kPTile, W><<<xcd_grid(nt2f, fx), 512, 0, c->stream>>>(                   \
-            tm2f, h2f, t2f, c->f_pos2.p, c->f_flag2.p, c->f_flag1.p, c->d_misc, xf2)
-                const bool pre2 = !(c->form_off & (kFormNoFbackPre | kFormFbackWide)) && !fx &&
-                                  tm2f.tsize == (uint32_t)kPTile2;
-                if (pre2 && (c->form_off & kFormFbackPre512))
-                    k_flags_back_pre<false, 6, kPTile2, 16><<<nt2f, 512, 0, c->stream>>>(
-                        tm2f, h2f, t2f, c->f_pos2.p, c->f_flag2.p, c->f_flag1.p, c->d_misc);
-                else if (pre2)
-                    k_flags_back_pre<false, 6, kPTile2, 32, 256><<<nt2f, 256, 0, c->stream>>>(
-                        tm2f, h2f, t2f, c->f_pos2.p, c->f_flag2.p, c->f_flag1.p, c->d_misc);
-                else if (c->form_off & kFormFbackWide) { CRDT_FBACK2(6, true); }
-                else if (c->fback_chk == 4) { CRDT_FBACK2(4, false); }
-                else if (c->fback_chk == 6) { CRDT_FBACK2(6, false); }
-                else { CRDT_FBACK2(0, false); }
-#undef CRDT_FBACK2
-                f1 = c->f_flag1.p;
-                // level 2 reused the tile -> segment index: rebuild level 1's
-                k_seg_index<<<std::min<uint32_t>(grid_for(nt1, 256), 4096), 256, 0, c->stream>>>(d_tb1, nseg, nt1,
-                                                                                                 c->p_tseg.p);
-            }
-            const bool fx1 = c->xcd_map && (c->form_off & kFormFbackXcd);
-            const uint32_t xf1 = fx1 ? (nt1 + kXcds - 1) / kXcds : 0;
-#define CRDT_FBACK1(CHK, W)                                                                               \
-    k_flags_back<true, CHK, kPTile, W><<<xcd_grid(nt1, fx1), 512, 0, c->stream>>>(                        \
-        tm1, hist1, c->p_toff.p, c->f_pos1.p, f1, dflags, c->d_misc, xf1)
-            if (fl) {
-                if (pt1)
-                    k_flags_back_pre<true, 6, kPTile, 14, 512, true><<<nt1, 512, 0, c->stream>>>(
-                        tm1, hist1, c->p_toff.p, c->f_pos1.p, f1, dflags, c->d_misc);
-                else if (!(c->form_off & (kFormNoFbackPre | kFormFbackWide)) && !fx1)
-                    k_flags_back_pre<true, 6, kPTile, 14><<<nt1, 512, 0, c->stream>>>(
-                        tm1, hist1, c->p_toff.p, c->f_pos1.p, f1, dflags, c->d_misc);
-                else if (c->form_off & kFormFbackWide) { CRDT_FBACK1(6, true); }
-                else if (c->fback_chk == 4) { CRDT_FBACK1(4, false); }
-                else if (c->fback_chk == 6) { CRDT_FBACK1(6, false); }
-                else { CRDT_FBACK1(0, false); }
-            }
-#undef CRDT_FBACK1
-        } else if (c->counts) {
-            k_resolve<true><<<max_items, kRThreads, 0, c->stream>>>(bst, d_ib, d_hb, c->p_ibucket.p, nb, rec, rv,
-                                                                    c->table, c->cap, c->d_Rj.p, jb, ps, cy, c->d_misc);
-            k_part_carry<false><<<dim3(kSKeys / 256, max_hot), 256, 0, c->stream>>>(d_hot, d_ib, d_hb, c->table,
-                                                                                    c->cap, ps, cy, c->d_Rj.p, jb, c->d_misc);
-            k_resolve<false><<<max_items, kRThreads, 0, c->stream>>>(bst, d_ib, d_hb, c->p_ibucket.p, nb, rec, rv,
-                                                                     c->table, c->cap, c->d_Rj.p, jb, ps, cy, c->d_misc);
-        } else if (pk) {   // packed order-free form: one LDS 64-bit max per record (sorted_path.inc)
-            uint64_t* ps_key = reinterpret_cast<uint64_t*>(c->p_kslt.p);
-            uint32_t* ps_val = c->p_ksu32.p;
-            const Rec12* rec12 = reinterpret_cast<const Rec12*>(rec);
-            // the split buckets' part folds + carry (they write the split buckets' rows) on the side stream, beside
-            // the unsplit buckets' resolve (the other rows): disjoint buckets, joined before the next window
-            // the sparse buckets in k_resolve_sparse's small workgroups (the dense ones skip them)
-            const bool spk = c->sparse_t > 0 && !(c->form_off & (kFormNoSparseK | kFormNoWholeLines));
-            // each kernel on exactly its items (k_item_lists; the host waits for the four counts — by then the GPU is
-            // at the resolve, and the launches below follow at once)
-            int st = CRDT_OK;
-            const bool lists = !c->has_comm && !(c->form_off & (kFormNoItemLists | kFormNoWholeLines));
-            uint32_t g_fold = max_items, g_dense = max_items, g_sparse = max_items, g_hot = max_hot;
-            const uint32_t *l_fold = nullptr, *l_dense = nullptr, *l_sparse = nullptr;
-            if (lists) {
-                uint32_t g_items;
-                if ((st = item_lists(spk ? c->hw_read : 0, spk ? c->sparse_t : 0, &g_fold, &g_dense, &g_sparse, &g_hot,
-                                     &g_items)))
-                    return st;
-                l_fold = c->p_ilist.p + kListHead;
-                l_dense = l_fold + max_items;
-                l_sparse = l_dense + max_items;
-            }
-            if ((st = ov ? overlap_fork(c) : CRDT_OK)) return st;
-            const hipStream_t fs = ov ? c->sstream : c->stream;
-            if (g_fold) {
-                if (cmp)
-                    k_resolve_packed<true, true, false, false, true><<<g_fold, kQThreads, 0, fs>>>(
-                        bst, d_ib, d_hb, c->p_ibucket.p, nb, rec12, nullptr, c->table, c->cap, c->hw_read, c->d_Rj.p, jb,
-                        ps_key, ps_val, pf, c->d_misc, EmitOut{}, 0, false, l_fold);
-                else if (k8)
-                    k_resolve_packed<true, true, true><<<g_fold, kQThreads, 0, fs>>>(
-                        bst, d_ib, d_hb, c->p_ibucket.p, nb, rec12, rv, c->table, c->cap, c->hw_read, c->d_Rj.p, jb, ps_key,
-                        ps_val, pf, c->d_misc, EmitOut{}, 0, false, l_fold);
-                else
-                    k_resolve_packed<true><<<g_fold, kQThreads, 0, fs>>>(
-                        bst, d_ib, d_hb, c->p_ibucket.p, nb, rec12, rv, c->table, c->cap, c->hw_read, c->d_Rj.p, jb, ps_key,
-                        ps_val, pf, c->d_misc, EmitOut{}, 0, false, l_fold);
-            }
-            if (g_hot)
-                k_part_carry_packed<false><<<dim3(kSKeys / 256, g_hot), 256, 0, fs>>>(
-                    d_hot, d_ib, d_hb, c->table, c->cap, c->hw_read, ps_key, ps_val, c->d_Rj.p, jb, pf, c->d_misc);
-            if (!g_dense) {
-            } else if (cmp)
-                k_resolve_packed<false, true, false, false, true><<<g_dense, kQThreads, 0, c->stream>>>(
-                    bst, d_ib, d_hb, c->p_ibucket.p, nb, rec12, nullptr, c->table, c->cap, c->hw_read, c->d_Rj.p, jb,
-                    ps_key, ps_val, pf, c->d_misc, EmitOut{}, c->sparse_t, spk, l_dense);
-            else if ((c->form_off & kFormNoWholeLines) && k8)      // (13-B records: 1-B key column)
-                k_resolve_packed<false, false, true><<<max_items, kQThreads, 0, c->stream>>>(
-                    bst, d_ib, d_hb, c->p_ibucket.p, nb, rec12, rv, c->table, c->cap, c->hw_read, c->d_Rj.p, jb, ps_key, ps_val,
-                    pf, c->d_misc);
-            else if (c->form_off & kFormNoWholeLines)
-                k_resolve_packed<false, false><<<max_items, kQThreads, 0, c->stream>>>(
-                    bst, d_ib, d_hb, c->p_ibucket.p, nb, rec12, rv, c->table, c->cap, c->hw_read, c->d_Rj.p, jb, ps_key, ps_val,
-                    pf, c->d_misc);
-            else if (k8)
-                k_resolve_packed<false, true, true><<<g_dense, kQThreads, 0, c->stream>>>(
-                    bst, d_ib, d_hb, c->p_ibucket.p, nb, rec12, rv, c->table, c->cap, c->hw_read, c->d_Rj.p, jb, ps_key, ps_val,
-                    pf, c->d_misc, EmitOut{}, c->sparse_t, spk, l_dense);
-            else
-                k_resolve_packed<false><<<g_dense, kQThreads, 0, c->stream>>>(
-                    bst, d_ib, d_hb, c->p_ibucket.p, nb, rec12, rv, c->table, c->cap, c->hw_read, c->d_Rj.p, jb, ps_key, ps_val,
-                    pf, c->d_misc, EmitOut{}, c->sparse_t, spk, l_dense);
-            if (!spk || !g_sparse) {
-            } else if (cmp)
-                k_resolve_sparse<false, true><<<g_sparse, kSpThreads, 0, c->stream>>>(
-                    bst, d_ib, c->p_ibucket.p, nb, rec12, nullptr, c->table, c->hw_read, c->d_Rj.p, jb, pf, c->d_misc,
-                    c->sparse_t, l_sparse);
-            else if (k8)
-                k_resolve_sparse<true, false><<<g_sparse, kSpThreads, 0, c->stream>>>(
-                    bst, d_ib, c->p_ibucket.p, nb, rec12, rv, c->table, c->hw_read, c->d_Rj.p, jb, pf, c->d_misc,
-                    c->sparse_t, l_sparse);
-            else
-                k_resolve_sparse<false, false><<<g_sparse, kSpThreads, 0, c->stream>>>(
-                    bst, d_ib, c->p_ibucket.p, nb, rec12, rv, c->table, c->hw_read, c->d_Rj.p, jb, pf, c->d_misc,
-                    c->sparse_t, l_sparse);
-            if (ov && (st = overlap_join(c))) return st;
-        } else {           // order-free list form; split buckets finished by k_part_carry<true>
-            k_resolve<true, true><<<max_items, kRThreads, 0, c->stream>>>(bst, d_ib, d_hb, c->p_ibucket.p, nb, rec,
-                                                                          rv, c->table, c->cap, c->d_Rj.p, jb, ps, cy,
-                                                                          c->d_misc);
-            k_part_carry<true><<<dim3(kSKeys / 256, max_hot), 256, 0, c->stream>>>(d_hot, d_ib, d_hb, c->table,
-                                                                                   c->cap, ps, cy, c->d_Rj.p, jb, c->d_misc);
-            k_resolve<false, true><<<max_items, kRThreads, 0, c->stream>>>(bst, d_ib, d_hb, c->p_ibucket.p, nb, rec,
-                                                                           rv, c->table, c->cap, c->d_Rj.p, jb, ps, cy,
-                                                                           c->d_misc);
-        }
-        if (ph) {
-            ev_record(c, ev_window(3, true));
-            c->sorted_phases = true;
-            c->p1_records = nw;
-        }
-        HIPCHK(hipGetLastError());
-        // the next window reads rows this one may have written anywhere below the capacity
-        c->hw_read = c->cap;
+        if (w.nw == 0) continue;
+        if ((st = sorted_window(c, f, cols, sg, w, dflags, emit))) return st;
     }
     if (em) return CRDT_OK;
     if (c->timing) {
@@ -3660,7 +3710,7 @@ int crdt_device_count(int* out) {
     return CRDT_OK;
 }
 
-// Tuning switches (DESIGN.md §9); with CRDT_ENV_DYNAMIC=1 re-read at every crdt_merge, so one
+// Tuning switches (DESIGN.md §8); with CRDT_ENV_DYNAMIC=1 re-read at every crdt_merge, so one
 // process can alternate them step by step (A/B runs on one memory placement: tools/ab_steps.sh).
 static void read_env_knobs(crdt_ctx* c) {
     if (const char* e = getenv("CRDT_NO_FUSE")) c->no_fuse = atoi(e) != 0;
